@@ -8,7 +8,8 @@ Gaussian noise with seeded random-init weights of the `scripts/train_unet.py:115
 region. N > 1: one process per GPU (torchrun), the global noise batch is generated from one seed and row-sharded,
 no collective inside the loop, one all_gather of the uint8 images at the end of each step ("scaling": "weak").
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields. A plain run sets up, warms up, times the --steps steps, writes the last
+step's outputs if --dump-outputs DIR is given, and prints the line — nothing else. With --full the line also carries
   roofline     — dominant kernel (since round 5 the Winograd F(4x4,3x3) fp32-MFMA convolution) measured LIVE with HIP events
                  around every launch of one extra eager forward on the same stream. `achieved`/`frac` are the EXECUTED
                  matrix-pipe FLOP/s against the 157.3 TF fp32 MFMA peak (a real roofline fraction, <= 1); the algorithmic
@@ -19,7 +20,12 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                  batch 16 per GPU, --mixed_precision bf16 (forward + backward + bucketed gradient all-reduce over RCCL +
                  clip + AdamW/EMA + weight re-pack); samples/s over all ranks;
   mel          — the audio codec either side of the loop (Mel.audio_slice_to_image / Mel.image_to_audio, batched),
-                 clips/s and algorithmic GB/s on device-resident buffers.
+                 clips/s and algorithmic GB/s on device-resident buffers;
+  configs      — BASELINE.json configs 1, 2 and 4 and the conditional model on this GPU.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float32;
+64 MB in all: an array larger than its share is replaced by a fixed, seeded sample of its elements), so that two builds can be
+compared output for output on identical inputs.
 
 Test hooks (never set by the driver): ADM_BENCH_EMU=1 runs the same code on the CPU-emulation build of the kernels over
 gloo at toy sizes (tests/test_bench_script.py launches this very file with 2 ranks); ADM_BENCH_FORCE_PG=1 builds the
@@ -67,6 +73,11 @@ def parse():
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--batch-per-gpu", type=int, default=32)
     p.add_argument("--ddim-steps", type=int, default=50)
+    p.add_argument("--full", action="store_true",
+                   help="also measure the side records (roofline, CPU baselines, BASELINE configs, Mel codec, config-5 training leg; in "
+                        "--mode train the one-rank group run); the --no-* options below apply to them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-graph", action="store_true")
     p.add_argument("--no-train-leg", action="store_true", help="skip the config-5 training sub-record")
@@ -85,6 +96,23 @@ def parse():
     p.add_argument("--mixed-precision", choices=["no", "bf16", "fp16"], default="bf16",
                    help="training precision: bf16 = BASELINE.json config 5 as written (bf16 MFMA operands, fp32 accumulate)")
     return p.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy in float32. Each array gets an equal share of DUMP_MAX_BYTES; a larger one is replaced by the
+    elements at a fixed, seeded set of flat indices (the same indices for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def self_launch(a):
@@ -156,7 +184,7 @@ class Job:
             dist.destroy_process_group()
 
 
-def train_leg(job, B, steps, warmup, mixed_precision):
+def train_leg(job, B, steps, warmup, mixed_precision, own_group=True, outputs=None):
     """scripts/train_unet.py's step (:226-267) on synthetic data: fused add_noise, native UNet forward + backward with the
     bucketed gradient all-reduce issued from inside the reverse pass, clip, fused AdamW + EMA, weight re-pack."""
     from audiodiffusion import DDPMScheduler, UNet2DModel
@@ -200,6 +228,8 @@ def train_leg(job, B, steps, warmup, mixed_precision):
         unet.refresh_weights()
 
     elapsed = job.timed(step, steps, warmup)
+    if outputs is not None:         # what the last timed step left: its loss and the updated master parameters / gradients
+        outputs.update(loss=torch.as_tensor(last["loss"]).reshape(1), params=flat.clone(), grads=grads.clone())
     value = job.world * B * steps / elapsed
     # every bucket of the last step was queued from inside the reverse pass — on EVERY rank (MIN over the job)
     every = None
@@ -208,7 +238,7 @@ def train_leg(job, B, steps, warmup, mixed_precision):
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         every = bool(int(ok.item()))
     own = None
-    if not job.pg and not dist.is_initialized() and os.environ.get("ADM_BENCH_TRAIN_PG", "1") == "1":
+    if own_group and not job.pg and not dist.is_initialized() and os.environ.get("ADM_BENCH_TRAIN_PG", "1") == "1":
         try:
             import socket
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -683,7 +713,10 @@ def main():
     world, rank, dev = job.world, job.rank, job.dev
 
     if a.mode == "train":
-        rec = train_leg(job, a.train_batch_per_gpu, a.steps, a.warmup, a.mixed_precision)
+        outs = {} if a.dump_outputs else None
+        rec = train_leg(job, a.train_batch_per_gpu, a.steps, a.warmup, a.mixed_precision, own_group=a.full, outputs=outs)
+        if outs and rank == 0:
+            dump_outputs(a.dump_outputs, outs)
         if rank == 0:
             rec.update({"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
                         "config": {"workload": rec.pop("workload"), "global_batch": rec["global_batch"],
@@ -712,10 +745,13 @@ def main():
     gathered = torch.empty((world * B, hw, hw, 1), dtype=torch.uint8, device=dev) if job.pg else None
     padded = torch.zeros((B, hw, hw, 1), dtype=torch.uint8, device=dev) if (job.pg and hi - lo < B) else None
 
+    last = {}
+
     def step():
         u8 = None
         if hi > lo:
-            _, u8 = pipe._denoise(noise, 0, 0.0, None, None, 0, 0, use_graph=not a.no_graph)
+            last["samples"], u8 = pipe._denoise(noise, 0, 0.0, None, None, 0, 0, use_graph=not a.no_graph)
+            last["images"] = u8
         if job.pg:
             if padded is not None:                      # a short (or empty) last shard: the gather takes equal-sized pieces
                 if u8 is not None:
@@ -727,6 +763,8 @@ def main():
 
     pipe.scheduler.set_timesteps(a.ddim_steps)
     elapsed = job.timed(step, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:    # rank 0's rows: the final float sample and the uint8 images, as the caller of the loop gets them
+        dump_outputs(a.dump_outputs, last)
 
     res = None
     if rank == 0:
@@ -747,7 +785,7 @@ def main():
         if EMU:
             res["config"]["workload"] = "TEST HOOK ADM_BENCH_EMU=1: toy UNet on the CPU emulation build over gloo (not a measurement)"
             res["gathered_checksum"] = int(gathered[:n_global].long().sum()) if gathered is not None else None
-        else:
+        elif a.full:
             # side legs never cost the headline line: a failure is reported in place
             try:
                 res["roofline"] = roofline(unet, noise, B)
@@ -776,7 +814,7 @@ def main():
                         if k in side_cpu and k in res["configs"]:
                             res["configs"][k]["cpu_baseline"] = side_cpu[k]
                 res["_side_cpu"] = side_cpu
-        if not a.no_mel_leg:
+        if a.full and not a.no_mel_leg:
             try:
                 res["mel"] = mel_leg(job)
             except Exception as e:  # noqa: BLE001 - a failing side leg must not cost the headline line
@@ -785,7 +823,7 @@ def main():
                 res["mel"]["cpu_baseline"] = res["_side_cpu"]["mel"]
     del pipe
     # config 5 beside the headline: every rank takes part (the gradient all-reduce is a collective)
-    if not a.no_train_leg:
+    if a.full and not a.no_train_leg:
         # The headline is measured; a side leg that HANGS (a collective that never completes on some rank) must not cost it:
         # every rank arms the same watchdog, rank 0 prints the line with the failure in place, all ranks leave.
         def give_up():

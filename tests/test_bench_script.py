@@ -34,7 +34,7 @@ def _run(n, extra=(), bare=False):
 
 
 def test_bench_py_two_ranks_prints_one_contract_line():
-    d = _run(2)
+    d = _run(2, ["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config"):
         assert k in d, k
@@ -78,7 +78,7 @@ def test_bench_py_result_is_independent_of_the_rank_count_and_a_bare_gpus_2_laun
 def test_bench_py_reports_a_hung_training_leg_beside_the_measured_headline():
     """The side legs run after the headline is measured; a training leg that does not come back (a collective some rank never
     reaches) must cost its own record only: every rank's watchdog fires, rank 0 prints the line with the failure in place."""
-    d = _run(2, ["--no-mel-leg", "--train-leg-timeout", "0.05"])
+    d = _run(2, ["--full", "--no-mel-leg", "--train-leg-timeout", "0.05"])
     assert d["value"] > 0 and d["n_gpus"] == 2
     assert "timeout" in d["train"]["error"]
 
@@ -88,7 +88,7 @@ def test_bench_py_eight_ranks_weak_with_the_training_leg_and_strong_against_one_
     """The world size BASELINE configs 3 and 5 are written for: 8 ranks (gloo, toy network on the emulator). Weak mode with the training
     leg — every gradient bucket all-reduced from inside the reverse pass on EVERY rank (MIN over the job) — and config 3 as written
     (`--scaling strong`: one global batch of 8 split by rows) against the same 8 rows on one rank: identical gathered images."""
-    d = _run(8, ["--batch-per-gpu", "1", "--no-mel-leg"])
+    d = _run(8, ["--full", "--batch-per-gpu", "1", "--no-mel-leg"])
     assert d["n_gpus"] == 8 and d["config"]["global_batch"] == 8 and d["scaling"] == "weak" and d["value"] > 0
     tr = d["train"]
     assert "error" not in tr, tr
@@ -107,9 +107,39 @@ def test_bench_py_eight_ranks_weak_with_the_training_leg_and_strong_against_one_
 def test_bench_py_one_rank_training_leg_runs_the_overlapped_all_reduce_in_its_own_group():
     """The driver's N = 1 line: no launcher, no process group — the training leg builds a one-rank group of its own so that the
     bucket-hook -> asynchronous all-reduce path executes under a real backward pass (every bucket, overlapped)."""
-    d = _run(1, ["--no-mel-leg"])
+    d = _run(1, ["--full", "--no-mel-leg"])
     tr = d["train"]
     assert "error" not in tr, tr
     own = tr["one_rank_group"]          # the headline of the leg is measured WITHOUT the group, the one-rank run is reported beside it
     assert "error" not in own and own["allreduce_buckets_overlapped"] == own["allreduce_buckets"] >= 1 and own["ms_per_step"] > 0
     assert tr["allreduce_overlapped_on_every_rank"] is None and tr["ms_per_step"] > 0
+
+
+def test_a_plain_run_times_the_headline_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line carries no side record; --dump-outputs writes what the last timed step returned (float32), and two runs
+    with the same arguments write the same arrays."""
+    import numpy as np
+    a = _run(1, ["--dump-outputs", str(tmp_path / "a")])
+    b = _run(1, ["--dump-outputs", str(tmp_path / "b")])
+    for k in ("roofline", "cpu_baseline", "configs", "mel", "train"):
+        assert k not in a, k
+    assert a["steps"] == 2 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["value"] > 0
+    shapes = {"samples": (2, 1, 16, 16), "images": (2, 16, 16, 1)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{n}.npy" for n in shapes)
+    for name, shape in shapes.items():
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == shape and np.isfinite(x).all()
+        assert np.array_equal(x, y), name
+    img = np.load(tmp_path / "a" / "images.npy")
+    assert img.min() >= 0 and img.max() <= 255 and np.array_equal(img, np.round(img)) and img.std() > 0
+
+
+def test_train_mode_dumps_the_loss_and_the_updated_parameters(tmp_path):
+    import numpy as np
+    d = _run(1, ["--mode", "train", "--train-batch-per-gpu", "2", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 2 and d["value"] > 0 and d["one_rank_group"] is None      # the one-rank group run is part of --full only
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.shape == (1,) and abs(float(loss[0]) - d["final_loss"]) <= 1e-6 * max(1.0, abs(d["final_loss"]))
+    for name in ("params", "grads"):
+        x = np.load(tmp_path / f"{name}.npy")
+        assert x.dtype == np.float32 and x.ndim == 1 and x.size > 0 and np.isfinite(x).all()

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT; cd $R; O=gpurun_out/$T; mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
 bash tools/pmc_forward.sh $T/pmc r06 2>&1 | tail -25 > $O/pmc.txt
 cp $O/pmc/r06_pmc_forward.json profiles/r06_pmc_forward.json          # so that the bench line below quotes THIS build's traffic
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_line.json 2> $O/bench_err.txt
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_line.json 2> $O/bench_err.txt
 cd /tmp && export TMPDIR=/tmp
 timeout 400 rocprofv3 --kernel-trace --stats -d $R/$O/trace -o bench -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs-leg > $R/$O/trace.log 2>&1
 DB=$(find $R/$O/trace -name "*.db" | head -1)
