@@ -45,6 +45,23 @@ class OpProfile(C.Structure):
     _fields_ = [("kind", C.c_int), ("variant", C.c_int), ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+PLAN_MAX_T, PLAN_MAX_R = 4, 12          # include/adm.h: ADM_PLAN_MAX_T / ADM_PLAN_MAX_R
+PLAN_GN_LOAD, PLAN_ACT, PLAN_STATS, PLAN_PER_SAMPLE_W, PLAN_GN_FUSE = 1, 2, 4, 8, 16
+
+
+class PlanRange(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_uint64)]
+
+
+class PlanOp(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int), ("hoist_from", C.c_int),
+        ("ks", C.c_int), ("stride", C.c_int), ("up", C.c_int), ("flags", C.c_int), ("gn_fuse", C.c_int),
+        ("n_tread", C.c_int), ("n_twrite", C.c_int), ("tread", C.c_int * PLAN_MAX_T), ("twrite", C.c_int * PLAN_MAX_T),
+        ("n_read", C.c_int), ("n_write", C.c_int), ("read", PlanRange * PLAN_MAX_R), ("write", PlanRange * PLAN_MAX_R),
+    ]
+
+
 class UNetConfig(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int), ("out_channels", C.c_int), ("layers_per_block", C.c_int), ("n_blocks", C.c_int),
@@ -104,6 +121,8 @@ _SIGS = {
     "adm_unet_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "adm_unet_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.POINTER(OpProfile), C.c_int,
                                    C.POINTER(C.c_int), C.c_void_p]),
+    "adm_unet_plan_ops": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlanOp), C.c_int, C.POINTER(C.c_int)]),
+    "adm_vae_plan_ops": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(PlanOp), C.c_int, C.POINTER(C.c_int)]),
     "adm_sample_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "adm_encode_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_int, C.c_void_p]),

@@ -79,6 +79,7 @@ void set_wgrad_max_split(int v);  // k_conv_wgrad.hip
 void bump_dispatch_epoch();        // net_exec.hip: a process-wide option changed -> training nets re-learn which packings they read
 unsigned dispatch_epoch();
 void set_blk_direct_dy(int v);     // net_exec.hip: option "blk_direct_dy" (read when a training plan is made)
+void set_side_overlap(int v);      // net_exec.hip: option "side_overlap" (read when an inference plan is made): -1 ADM_SIDE_OVERLAP (default 1) | 0 off | 1 on
 long winograd_packed_floats(int Cout, int Cin, int transposed);   // size of a wu / wuT buffer: the F(2x2) image (+ the F(4x4) image where conv_wino6_kernel may run)
 void set_single_sample(int v);     // "single_sample" (k_conv_mfma.hip): 0 (default) off | 1 the single-sample partition rules (conv_wino4_kernel split K, 16-part 3x3 split on <= 8x8 planes)
 bool conv_single_sample(const adm_conv_args& a);   // the call's (= its model's) rule, else the option

@@ -167,7 +167,12 @@ struct Net {
   void* ev_fork = nullptr;           // hipEvent_t (opaque here: the emulator has no events)
   void* ev_join = nullptr;
   int plan_side_overlap(int B);
-  int launch_side_conv(const Op& o, int B, const float* temb_all, int temb_stride, hipStream_t st);
+  int launch_side_conv(size_t j, int B, const float* temb_all, int temb_stride, hipStream_t st);
+  // the arguments convolution op oi is launched with on the product path (fill_conv_args + the statistics epilogue); returns the GroupNorm op
+  // whose scale / shift its split-K finish pass is offered (-1: none). run() launches from it, plan_report() derives byte ranges from it.
+  int conv_launch_args(size_t oi, int B, const float* temb_all, int temb_stride, adm_conv_args* a) const;
+  // adm_unet_plan_ops / adm_vae_plan_ops: one record per op of the current plan (planned_B) — tensors and device byte ranges read / written
+  int plan_report(const float* temb_all, int temb_stride, adm_plan_op* recs, int cap, int* n_out) const;
   std::vector<char> bias_done;       // per op, during a reverse walk: its bias gradient came with another convolution's channel sums
   float *tmp_da = nullptr, *wgrad_ws = nullptr, *s12 = nullptr, *tmp_w = nullptr;
   size_t tmp_da_floats = 0, wgrad_ws_floats = 0, tmp_w_floats = 0;

@@ -735,6 +735,16 @@ static unsigned packing_of_variant(int var, bool fwd) {
   return fwd ? PK_WP : PK_WPT;                              // direct MFMA / small-channel kernels
 }
 
+// Option "side_overlap" (adm_set_option): -1 follows ADM_SIDE_OVERLAP (default on), 0 off, 1 on; read when an inference plan is made (a changed
+// value moves the dispatch epoch, so every net re-plans on its next call).
+static std::atomic<int> g_side_overlap{-1};
+void set_side_overlap(int v) { g_side_overlap.store(v); }
+static bool side_overlap_on() {
+  static const int env = [] { const char* e = getenv("ADM_SIDE_OVERLAP"); return e ? atoi(e) : 1; }();
+  const int v = g_side_overlap.load();
+  return (v < 0 ? env : v) != 0;
+}
+
 // Which convolutions run on the side stream (see net_exec.h). Op j qualifies when it is a plain 1x1 convolution (no GroupNorm / activation on
 // its load path, no statistics epilogue, weights of its own), its inputs are produced at least two ops before it, and NO tensor dies between the
 // hoist point and j: the arena hands a dead tensor's buffer to later outputs in op order, and only with no death in the window can neither j's
@@ -743,8 +753,7 @@ int Net::plan_side_overlap(int B) {
   const int n = (int)ops.size();
   hoist_from.assign(n, -1);
   hoist_at.assign(n, {});
-  static const int on = [] { const char* e = getenv("ADM_SIDE_OVERLAP"); return e ? atoi(e) : 1; }();
-  if (training || !on) return 0;
+  if (training || !side_overlap_on()) return 0;
   std::vector<int> prod(tensors.size(), -1), deaths(n, 0);
   for (int i = 0; i < n; ++i) if (ops[i].out >= 0) prod[ops[i].out] = i;
   for (const Tensor& t : tensors) if (!t.external && t.last_use >= 0 && t.last_use < n) ++deaths[t.last_use];
@@ -781,12 +790,21 @@ int Net::plan_side_overlap(int B) {
   return 0;
 }
 
-int Net::launch_side_conv(const Op& o, int B, const float* temb_all, int temb_stride, hipStream_t st) {
+int Net::launch_side_conv(size_t j, int B, const float* temb_all, int temb_stride, hipStream_t st) {
+  const Op& o = ops[j];
   adm_conv_args a;
-  fill_conv_args(o, B, temb_all, temb_stride, &a);
+  ADM_REQUIRE(conv_launch_args(j, B, temb_all, temb_stride, &a) < 0 && a.stats_out == nullptr, "side launch with a statistics epilogue");
   ADM_TRY(launch_conv2d(a, st));
   if (o.w) ADM_TRY(note_packing(*o.w, packing_of_variant(last_conv_variant(), true)));
   return 0;
+}
+
+int Net::conv_launch_args(size_t oi, int B, const float* temb_all, int temb_stride, adm_conv_args* a) const {
+  const Op& o = ops[oi];
+  fill_conv_args(o, B, temb_all, temb_stride, a);
+  if (tensors[o.out].stats != nullptr && !training) { a->stats_out = tensors[o.out].stats; a->stats_tiles = tensors[o.out].stat_tiles; }
+  const int gk = oi < gn_fuse_of.size() ? gn_fuse_of[oi] : -1;
+  return gk >= 0 && tensors[o.out].stats == nullptr ? gk : -1;
 }
 
 void Net::fill_conv_args(const Op& o, int B, const float* temb_all, int temb_stride, adm_conv_args* ap) const {
@@ -837,10 +855,11 @@ int Net::run(const float* x, float* out, int B, const float* temb_all, int temb_
 #if !defined(ADM_EMU)
         ADM_HIP_OK(hipEventRecord((hipEvent_t)ev_fork, st));            // everything enqueued so far (the inputs' producers) ...
         ADM_HIP_OK(hipStreamWaitEvent(side, (hipEvent_t)ev_fork, 0));    // ... precedes the side launch
-        ADM_TRY(launch_side_conv(ops[j], B, temb_all, temb_stride, side));
+        ADM_TRY(launch_side_conv(j, B, temb_all, temb_stride, side));
         ADM_HIP_OK(hipEventRecord((hipEvent_t)ev_join, side));
 #else
-        ADM_TRY(launch_side_conv(ops[j], B, temb_all, temb_stride, st));  // emulator: the hoisted ORDER, in line (exercises the buffer-reuse rule)
+        ADM_TRY(launch_side_conv(j, B, temb_all, temb_stride, st));  // emulator: the hoisted ORDER, in line (exercises the buffer-reuse rule; it
+                                                                      // cannot see a window op that overwrites what j has already read: tests/test_side_overlap.py)
 #endif
       }
       if (hoist_from[oidx] >= 0) {                                   // its own position: join
@@ -873,9 +892,8 @@ int Net::run(const float* x, float* out, int B, const float* temb_all, int temb_
       }
     } else if (o.kind == Op::CONV) {
       adm_conv_args a;
-      fill_conv_args(o, B, temb_all, temb_stride, &a);
-      if (tensors[o.out].stats != nullptr && !training) { a.stats_out = tensors[o.out].stats; a.stats_tiles = tensors[o.out].stat_tiles; }
       const size_t oi = (size_t)(&o - ops.data());
+      const int gk = conv_launch_args(oi, B, temb_all, temb_stride, &a);
       const BlkOp* bo = (training && conv_bf16_mode() >= 3 && oi < blk.size() && blk[oi].xa != nullptr) ? &blk[oi] : nullptr;
       if (bo)    // level 3: the activated input once as a blocked 16-bit image (kept for the weight gradient)
         ADM_TRY(launch_blk_apply(a.x1, a.C1, a.x1_bstride, a.x2, a.C2, a.x2_bstride, B, a.H, a.W, a.gn_scale, a.gn_shift, a.act, bo->xa,
@@ -884,8 +902,7 @@ int Net::run(const float* x, float* out, int B, const float* temb_all, int temb_
         // the first single-input GroupNorm that reads this output, announced to the launch: a split-K finish pass that can leave its
         // scale / shift takes the request (k_groupnorm.hip), and the statistics op below is then skipped
         GnFuse gf;
-        const int gk = oi < gn_fuse_of.size() ? gn_fuse_of[oi] : -1;
-        const bool ask = gk >= 0 && tensors[o.out].stats == nullptr;
+        const bool ask = gk >= 0;
         if (ask) {
           const Op& go = ops[gk];
           const GnBuf& gb = gnbufs[go.gn];
@@ -939,6 +956,128 @@ int Net::run(const float* x, float* out, int B, const float* temb_all, int temb_
     }
   }
   tm->finish();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- Net: plan report (test aid)
+// What every op of the current plan reads and writes, from the same fields run() launches with (convolutions: conv_launch_args). A range over
+// `floats` elements starting at p; one of `n` samples lies `bstride` elements after the previous one (0: packed), so channel slices report
+// the span from the first sample's slice to the end of the last one's.
+namespace {
+struct PlanRec {
+  adm_plan_op* r;
+  int tensor(bool write, int t) {
+    if (t < 0) return 0;
+    int* ids = write ? r->twrite : r->tread;
+    int& n = write ? r->n_twrite : r->n_tread;
+    for (int i = 0; i < n; ++i) if (ids[i] == t) return 0;
+    ADM_REQUIRE(n < ADM_PLAN_MAX_T, "plan_report: more than ADM_PLAN_MAX_T tensors for one op");
+    ids[n++] = t;
+    return 0;
+  }
+  int range(bool write, const void* p, size_t bytes) {
+    if (p == nullptr || bytes == 0) return 0;
+    adm_plan_range* rs = write ? r->write : r->read;
+    int& n = write ? r->n_write : r->n_read;
+    ADM_REQUIRE(n < ADM_PLAN_MAX_R, "plan_report: more than ADM_PLAN_MAX_R ranges for one op");
+    rs[n].lo = (uint64_t)(uintptr_t)p;
+    rs[n].hi = rs[n].lo + bytes;
+    ++n;
+    return 0;
+  }
+  int floats(bool write, const float* p, int n_samples, long bstride, long per_sample) {
+    const long span = (long)(n_samples - 1) * (bstride ? bstride : per_sample) + per_sample;
+    return range(write, p, sizeof(float) * (size_t)span);
+  }
+};
+}  // namespace
+
+int Net::plan_report(const float* temb_all, int temb_stride, adm_plan_op* recs, int cap, int* n_out) const {
+  ADM_REQUIRE(planned_B > 0 && hoist_from.size() == ops.size(), "plan_report: the net is not planned");
+  const int B = planned_B;
+  *n_out = (int)ops.size();
+  for (size_t oi = 0; oi < ops.size() && (int)oi < cap; ++oi) {
+    const Op& o = ops[oi];
+    adm_plan_op& r = recs[oi];
+    memset(&r, 0, sizeof(r));
+    r.kind = (int)o.kind;
+    r.hoist_from = hoist_from[oi];
+    r.gn_fuse = -1;
+    PlanRec pr{&r};
+    // an activation tensor: its id, and its bytes unless it is the caller's memory (network input / output: set per call)
+    auto whole = [&](bool write, int t) -> int {
+      if (t < 0) return 0;
+      ADM_TRY(pr.tensor(write, t));
+      const Tensor& tt = tensors[t];
+      if (tt.external) return 0;
+      ADM_TRY(pr.range(write, tt.ptr, sizeof(float) * (size_t)B * tt.C * tt.H * tt.W));
+      if (!write && tt.stats != nullptr && o.kind == Op::GN)       // a folded GroupNorm reads the producer's partial sums
+        ADM_TRY(pr.range(false, tt.stats, sizeof(double) * 2 * (size_t)B * tt.C * tt.stat_tiles));
+      return 0;
+    };
+    auto gnbuf = [&](bool write, const GnBuf& g) -> int {
+      ADM_TRY(pr.floats(write, g.scale, 1, 0, (long)B * g.C));
+      ADM_TRY(pr.floats(write, g.shift, 1, 0, (long)B * g.C));
+      ADM_TRY(pr.floats(write, g.mean_rstd, 1, 0, (long)B * groups * 2));
+      return 0;
+    };
+    if (o.kind == Op::CONV) {
+      adm_conv_args a;
+      const int gk = conv_launch_args(oi, B, temb_all, temb_stride, &a);
+      int Ho, Wo;
+      conv_out_dims(a.H, a.W, a.up, a.stride, a.ks, a.pad_lo, &Ho, &Wo);
+      const long plane = (long)a.H * a.W, oplane = (long)Ho * Wo, Cin = a.C1 + a.C2;
+      r.ks = a.ks; r.stride = a.stride; r.up = a.up; r.gn_fuse = gk;
+      r.flags = (a.gn_scale ? ADM_PLAN_GN_LOAD : 0) | (a.act ? ADM_PLAN_ACT : 0) | (a.stats_out ? ADM_PLAN_STATS : 0) |
+                (o.wt >= 0 ? ADM_PLAN_PER_SAMPLE_W : 0) | (gk >= 0 ? ADM_PLAN_GN_FUSE : 0);
+      for (int t : {o.in1, o.in2, o.res, o.wt}) ADM_TRY(pr.tensor(false, t));
+      ADM_TRY(pr.tensor(true, o.out));
+      if (!tensors[o.in1].external) ADM_TRY(pr.floats(false, a.x1, B, a.x1_bstride, (long)a.C1 * plane));
+      if (o.in2 >= 0 && !tensors[o.in2].external) ADM_TRY(pr.floats(false, a.x2, B, a.x2_bstride, (long)a.C2 * plane));
+      if (a.gn_scale) {
+        ADM_TRY(pr.floats(false, a.gn_scale, 1, 0, (long)B * Cin));
+        ADM_TRY(pr.floats(false, a.gn_shift, 1, 0, (long)B * Cin));
+      }
+      if (o.wt >= 0) {
+        ADM_TRY(pr.floats(false, a.wpacked, B, a.w_bstride, Cin * a.ks * a.ks * a.Cout));
+      } else {
+        ADM_TRY(pr.floats(false, a.wpacked, 1, 0, Cin * a.ks * a.ks * a.Cout));
+        if (a.wino_packed) ADM_TRY(pr.floats(false, a.wino_packed, 1, 0, winograd_packed_floats(a.Cout, (int)Cin, 0)));
+        if (a.bf16_packed) ADM_TRY(pr.range(false, a.bf16_packed, 2 * (size_t)Cin * a.ks * a.ks * a.Cout));
+      }
+      ADM_TRY(pr.floats(false, a.bias, 1, 0, a.Cout));
+      if (a.chan_add) ADM_TRY(pr.floats(false, a.chan_add, B, a.chan_add_stride, a.Cout));
+      if (a.residual && !tensors[o.res].external) ADM_TRY(pr.floats(false, a.residual, B, 0, (long)a.Cout * oplane));
+      if (!tensors[o.out].external) ADM_TRY(pr.floats(true, a.out, B, 0, (long)a.Cout * oplane));
+      if (a.stats_out) ADM_TRY(pr.range(true, a.stats_out, sizeof(double) * 2 * (size_t)B * a.Cout * a.stats_tiles));
+      if (gk >= 0) ADM_TRY(gnbuf(true, gnbufs[ops[gk].gn]));      // the finish pass may take the request (decided per launch)
+      continue;
+    }
+    switch (o.kind) {
+      case Op::GN:        // reads the activations (or the producers' partial sums), writes scale / shift
+        ADM_TRY(whole(false, o.in1)); ADM_TRY(whole(false, o.in2));
+        ADM_TRY(pr.floats(false, o.g->gamma, 1, 0, o.g->C)); ADM_TRY(pr.floats(false, o.g->beta, 1, 0, o.g->C));
+        ADM_TRY(gnbuf(true, gnbufs[o.gn]));
+        break;
+      case Op::LN:
+        ADM_TRY(whole(false, o.in1));
+        ADM_TRY(pr.floats(false, o.g->gamma, 1, 0, o.g->C)); ADM_TRY(pr.floats(false, o.g->beta, 1, 0, o.g->C));
+        ADM_TRY(whole(true, o.out));
+        break;
+      case Op::XATTN: {
+        const Tensor& t1 = tensors[o.in1];
+        ADM_TRY(whole(false, o.in1));
+        if (ctx != nullptr) ADM_TRY(pr.floats(false, ctx, 1, 0, (long)B * ctx_S * ctx_D));
+        ADM_TRY(pr.floats(false, o.wk, 1, 0, (long)t1.C * ctx_D)); ADM_TRY(pr.floats(false, o.wv, 1, 0, (long)t1.C * ctx_D));
+        ADM_TRY(whole(true, o.out));
+        break;
+      }
+      default:            // ATTN, GEGLU, TRANSP (a channel slice of in1: the whole tensor), SOFTMAXC (in place: out == in1, read and written)
+        ADM_TRY(whole(false, o.in1));
+        ADM_TRY(whole(true, o.out));
+        break;
+    }
+  }
   return 0;
 }
 

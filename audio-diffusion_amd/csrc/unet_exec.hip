@@ -167,6 +167,7 @@ static int finalize(adm_unet* h) {
   b.groups = c.norm_num_groups;
   b.eps = c.norm_eps;
   b.training = h->training;
+  b.ctx_D = c.cross_attention_dim;      // (adm_unet_set_encoding sets the same; the plan report sizes the to_k / to_v weights with it)
   int rc = 0;
   b.t_in = b.new_tensor(c.in_channels, c.sample_h, c.sample_w, true);
   const ConvW* w;
@@ -624,6 +625,13 @@ int adm_unet_profile(adm_unet_t* h, const float* x, float timestep, float* out, 
   *n_out = (int)v.size();
   for (int i = 0; i < (int)v.size() && i < cap; ++i) recs[i] = v[i];
   return 0;
+}
+
+int adm_unet_plan_ops(adm_unet_t* h, int B, adm_plan_op* recs, int cap, int* n_out) {
+  ADM_REQUIRE(h && B > 0 && (recs || cap == 0) && n_out, "unet_plan_ops: bad argument");
+  ADM_TRY(finalize(h));
+  ADM_TRY(plan(h, B));
+  return h->net.plan_report(h->temb_all, h->temb_rows, recs, cap, n_out);
 }
 
 int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,

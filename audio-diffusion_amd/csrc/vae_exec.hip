@@ -144,6 +144,28 @@ static int vae_finalize(adm_vae* h) {
   return 0;
 }
 
+// (re-)plan the encoder / decoder for batch B, with its per-batch scratch (also when an option set since has moved the dispatch epoch)
+static int vae_plan_enc(adm_vae* h, int B, hipStream_t st) {
+  if (h->planned_B_enc == B && h->enc.plan_current(B)) return 0;
+  ADM_TRY(stream_sync(st));
+  ADM_TRY(h->enc.plan(B));
+  if (h->moments) dfree(h->moments);
+  h->moments = nullptr;
+  ADM_TRY(dmalloc((void**)&h->moments, sizeof(float) * (size_t)B * 2 * h->cfg.latent_channels * h->lat_h * h->lat_w));
+  h->planned_B_enc = B;
+  return 0;
+}
+static int vae_plan_dec(adm_vae* h, int B, hipStream_t st) {
+  if (h->planned_B_dec == B && h->dec.plan_current(B)) return 0;
+  ADM_TRY(stream_sync(st));
+  ADM_TRY(h->dec.plan(B));
+  if (h->zq) dfree(h->zq);
+  h->zq = nullptr;
+  ADM_TRY(dmalloc((void**)&h->zq, sizeof(float) * (size_t)B * h->cfg.latent_channels * h->lat_h * h->lat_w));
+  h->planned_B_dec = B;
+  return 0;
+}
+
 }  // namespace adm
 
 extern "C" {
@@ -192,13 +214,7 @@ int adm_vae_encode(adm_vae_t* h, const float* x, const float* noise, float out_s
   ADM_TRY(vae_finalize(h));
   const int Cz = h->cfg.latent_channels;
   const long hw = (long)h->lat_h * h->lat_w;
-  if (h->planned_B_enc != B || !h->enc.plan_current(B)) {
-    ADM_TRY(stream_sync(st));
-    ADM_TRY(h->enc.plan(B));
-    if (h->moments) dfree(h->moments);
-    ADM_TRY(dmalloc((void**)&h->moments, sizeof(float) * (size_t)B * 2 * Cz * hw));
-    h->planned_B_enc = B;
-  }
+  ADM_TRY(vae_plan_enc(h, B, st));
   float* mom = moments_out ? moments_out : h->moments;
   ADM_TRY(h->enc.run(x, mom, B, nullptr, 0, st, nullptr));
   return launch_gaussian_sample(mom, noise, z_out, B, Cz, hw, out_scale, st);
@@ -209,19 +225,20 @@ int adm_vae_decode(adm_vae_t* h, const float* z, float in_scale, float* out, int
   hipStream_t st = (hipStream_t)stream;
   ADM_TRY(vae_finalize(h));
   const long n = (long)B * h->cfg.latent_channels * h->lat_h * h->lat_w;
-  if (h->planned_B_dec != B || !h->dec.plan_current(B)) {
-    ADM_TRY(stream_sync(st));
-    ADM_TRY(h->dec.plan(B));
-    if (h->zq) dfree(h->zq);
-    ADM_TRY(dmalloc((void**)&h->zq, sizeof(float) * (size_t)n));
-    h->planned_B_dec = B;
-  }
+  ADM_TRY(vae_plan_dec(h, B, st));
   const float* zin = z;
   if (in_scale != 1.0f) {
     ADM_TRY(launch_scale(z, h->zq, in_scale, n, st));
     zin = h->zq;
   }
   return h->dec.run(zin, out, B, nullptr, 0, st, nullptr);
+}
+
+int adm_vae_plan_ops(adm_vae_t* h, int which, int B, adm_plan_op* recs, int cap, int* n_out) {
+  ADM_REQUIRE(h && (which == 0 || which == 1) && B > 0 && (recs || cap == 0) && n_out, "vae_plan_ops: bad argument");
+  ADM_TRY(vae_finalize(h));
+  ADM_TRY(which == 0 ? vae_plan_enc(h, B, nullptr) : vae_plan_dec(h, B, nullptr));
+  return (which == 0 ? h->enc : h->dec).plan_report(nullptr, 0, recs, cap, n_out);
 }
 
 }  // extern "C"

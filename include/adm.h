@@ -64,8 +64,11 @@ int adm_has_experiments(void);
  * "gn_fuse_finish" = 1 (default) a split-K convolution (output planes of <= 8x8 pixels) whose output a GroupNorm reads next leaves
  *   that GroupNorm's scale / shift from its finish pass (one launch instead of finish + statistics; the tensor is bit-identical) |
  *   0 separate launches | -1 ADM_GN_FUSE_FINISH.
+ * "side_overlap" = 1 (default) inference plans launch the 1x1 convolutions whose inputs are ready a few ops early (the resnets' conv_shortcut)
+ *   on a second stream beside those ops (scheduling only: bit-identical results; adm_plan_op.hoist_from shows where) | 0 every op in list
+ *   order on the caller's stream | -1 ADM_SIDE_OVERLAP. Every net re-plans on its next call (a UNet's captured loop is re-captured).
  * The dispatch epoch moves only when a value really changes; set options BEFORE adm_unet_refresh_weights / the next train step.
- * adm_version() = 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
+ * adm_version() = 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
 int adm_set_option(const char* name, int value);
 /* Per-(device, stream) scratch the library keeps for a stream (the split-K slab buffer of the small-plane convolutions, >= 1 MiB, at most
  * 1024 streams per device): give it back BEFORE destroying a stream that has run library calls. Drains the stream first (a captured graph of
@@ -285,6 +288,32 @@ size_t adm_unet_workspace_bytes(adm_unet_t* h);
 typedef struct adm_op_profile { int kind, variant; float ms; double flops, bytes; } adm_op_profile;
 int adm_unet_profile(adm_unet_t* h, const float* x, float timestep, float* out, int B, adm_op_profile* recs, int cap,
                      int* n_out, void* stream);
+/* Test aid (adm_version() >= 105): the inference plan of a net at batch B, one record per op in list order — what each op reads and writes and
+ * where the side-stream overlap ("side_overlap") launches it. Plans the net at B first if it is not planned (outside any capture, exactly as a
+ * forward would; a UNet's captured loop is dropped then). Byte ranges come from the arguments the launches are made with (adm_conv_args for
+ * convolutions, including the statistics epilogue and the GroupNorm scale / shift a split-K finish pass may leave); they may over-approximate
+ * (a channel slice reports the span of every sample's slice) and never under-approximate the plan's own memory. The network input and output
+ * and the per-stream split-K slab are not plan memory: the first two appear by tensor id only, the slab not at all (each stream has its own).
+ * n_out receives the op count; at most cap records are written. */
+#define ADM_PLAN_GN_LOAD 1        /* convolution: GroupNorm affine on its load path */
+#define ADM_PLAN_ACT 2            /* convolution: SiLU on its load path */
+#define ADM_PLAN_STATS 4          /* convolution: GroupNorm partial sums from its epilogue (stats_out) */
+#define ADM_PLAN_PER_SAMPLE_W 8   /* convolution: weights taken from an activation tensor */
+#define ADM_PLAN_GN_FUSE 16       /* convolution: offered the scale / shift of GroupNorm op gn_fuse (its split-K finish pass may write them) */
+#define ADM_PLAN_MAX_T 4
+#define ADM_PLAN_MAX_R 12
+typedef struct adm_plan_range { uint64_t lo, hi; } adm_plan_range;   /* device bytes [lo, hi) */
+typedef struct adm_plan_op {
+  int kind;        /* 0 GroupNorm statistics, 1 convolution, 2 attention core, 3 channel softmax (in place), 4 transpose, 5 LayerNorm, 6 GEGLU,
+                    * 7 cross-attention */
+  int hoist_from;  /* -1: in place; i >= 0: launched on the side stream in front of op i and joined at its own position */
+  int ks, stride, up, flags, gn_fuse;             /* convolutions (gn_fuse: the GroupNorm op offered, -1 none) */
+  int n_tread, n_twrite;
+  int tread[ADM_PLAN_MAX_T], twrite[ADM_PLAN_MAX_T];   /* activation tensor ids */
+  int n_read, n_write;
+  adm_plan_range read[ADM_PLAN_MAX_R], write[ADM_PLAN_MAX_R];
+} adm_plan_op;
+int adm_unet_plan_ops(adm_unet_t* h, int B, adm_plan_op* recs, int cap, int* n_out);
 
 /* ---- training (rows T4,T5; scripts/train_unet.py:257-259): the master parameters live in ONE caller-owned flat fp32
  * device buffer (so the fused optimizer kernel can update them in a single launch); call order:
@@ -343,6 +372,8 @@ int adm_vae_encode(adm_vae_t* h, const float* x, const float* noise, float out_s
                    int B, void* stream);
 /* out (B,Cout,H,W) = decoder(post_quant_conv(in_scale * z)); in_scale carries the reference's 1/0.18215. */
 int adm_vae_decode(adm_vae_t* h, const float* z, float in_scale, float* out, int B, void* stream);
+/* The plan report of adm_unet_plan_ops for the encoder (which = 0, quant_conv included) or the decoder (1, post_quant_conv included). */
+int adm_vae_plan_ops(adm_vae_t* h, int which, int B, adm_plan_op* recs, int cap, int* n_out);
 
 /* ---------------------------------------------------------------- training-step optimizer side (rows T4,T6,T7,T9)
  * scripts/train_unet.py:258-267 over FLAT fp32 buffers (all parameters / grads / moments / EMA shadow contiguous).
