@@ -159,6 +159,11 @@ long conv_wgrad_workspace(const adm_conv_args& a, int* split_out);
 int launch_conv_wgrad(const adm_conv_args& a, const float* dy, float* dW, int accumulate, float* workspace, hipStream_t st);
 
 // k_attention.hip
+// kernel family the last attention launcher on this thread dispatched to: family * 100 + head_dim (include/adm.h: adm_last_attention_variant);
+// set by every launcher below and in k_transformer.hip / k_backward.hip once its arguments are accepted, thread-local like the convolutions'.
+enum AttnFamily { ATT_ONE_PASS = 1, ATT_SPLIT4 = 2, ATT_BLOCKED = 3, ATT_MFMA = 4, ATT_CROSS = 5, ATT_BWD = 6, ATT_BWD_BLOCKED = 7, ATT_CROSS_BWD = 8 };
+int last_attention_variant();
+void set_last_attention_variant(int family, int head_dim);
 int launch_attention(const float* qkv, float* out, int N, int C, int T, int head_dim, hipStream_t st, int single_sample = 0);   // single_sample: the model's rule (0 = the option)
 
 // k_transformer.hip (UNet2DConditionModel: Transformer2DModel blocks)

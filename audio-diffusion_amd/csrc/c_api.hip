@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 105; }   // 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 106; }   // 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -85,6 +85,7 @@ int adm_set_option(const char* name, int value) {
   return 0;
 }
 int adm_last_conv_variant(void) { return adm::last_conv_variant(); }
+int adm_last_attention_variant(void) { return adm::last_attention_variant(); }
 int adm_release_stream(void* stream) { adm::conv_ksplit_release((hipStream_t)stream); return 0; }
 int adm_has_experiments(void) { return 0; }   // (kept for ABI stability: the experiments builds were retired in round 6)
 int adm_is_device_build(void) {

@@ -125,6 +125,10 @@ __global__ void __launch_bounds__(256) attention_split4_kernel(const float* __re
   for (int d = 0; d < D; ++d) ob[(long)d * T + t] = o[d] * inv;
 }
 
+static thread_local int g_last_attention_variant = 0;
+int last_attention_variant() { return g_last_attention_variant; }
+void set_last_attention_variant(int family, int head_dim) { g_last_attention_variant = family * 100 + head_dim; }
+
 int launch_attention(const float* qkv, float* out, int N, int C, int T, int head_dim, hipStream_t st, int single_sample) {
   ADM_REQUIRE(C % head_dim == 0, "attention: C not divisible by head_dim");
   const int heads = C / head_dim;
@@ -139,6 +143,7 @@ int launch_attention(const float* qkv, float* out, int N, int C, int T, int head
   const float scale = 1.0f / sqrtf((float)head_dim);
   if (single_sample_rule(single_sample) && T >= 64 && T % 4 == 0 && (head_dim == 8 || head_dim == 4 || head_dim == 16)) {
     const dim3 g4(ceil_div(T, 64), heads, N);
+    set_last_attention_variant(ATT_SPLIT4, head_dim);
     if (head_dim == 8) ADM_LAUNCH((attention_split4_kernel<8>), g4, dim3(256), smem, st, qkv, out, C, T, scale);
     else if (head_dim == 4) ADM_LAUNCH((attention_split4_kernel<4>), g4, dim3(256), smem, st, qkv, out, C, T, scale);
     else ADM_LAUNCH((attention_split4_kernel<16>), g4, dim3(256), smem, st, qkv, out, C, T, scale);
@@ -146,6 +151,7 @@ int launch_attention(const float* qkv, float* out, int N, int C, int T, int head
   }
 #define ADM_ATT_CASE(DD)                                                                  \
   if (head_dim == DD) {                                                                   \
+    set_last_attention_variant(ATT_ONE_PASS, DD);                                         \
     ADM_LAUNCH((attention_kernel<DD>), grid, block, smem, st, qkv, out, C, T, scale);     \
     return ADM_CHECK_LAUNCH();                                                            \
   }

@@ -291,17 +291,20 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
       for (int d = 0; d < D; ++d) s = fmaf(q[d], Ks[j * D + d], s);
       m = fmaxf(m, s * scale);
     }
-    float l = 0.f, dsum = 0.f;   // l = sum p~, dsum = sum p~ (go . v_j)
+    // l = sum p~, dsum = sum p~ (go . v_j), both in double: dq_i = scale * sum_j p_ij (gv_ij - D_i) k_j is what is left of a cancellation against
+    // D_i = dsum / l, so the rounding of two serial fp32 sums over all T keys came out 14x above torch's fp32 error at T = 1056
+    // (tests/test_attention_sweep.py, profiles/attention_accuracy.md); two conversions and two f64 operations per key.
+    double l = 0.0, dsum = 0.0;
     for (int j = 0; j < T; ++j) {
       float s = 0.f, gv = 0.f;
       ADM_UNROLL
       for (int d = 0; d < D; ++d) { s = fmaf(q[d], Ks[j * D + d], s); gv = fmaf(go[d], Vs[j * D + d], gv); }
       const float pj = __expf(s * scale - m);
-      l += pj;
-      dsum = fmaf(pj, gv, dsum);
+      l += (double)pj;
+      dsum = fma((double)pj, (double)gv, dsum);
     }
-    const float inv = 1.0f / l;
-    const float Di = dsum * inv;   // = dout_i . out_i
+    const float inv = (float)(1.0 / l);
+    const float Di = (float)(dsum / l);   // = dout_i . out_i
     Ms[i] = m; Ls[i] = inv; Ds[i] = Di;
     float dq[D];
     ADM_UNROLL
@@ -652,6 +655,7 @@ int launch_attention_bwd(const float* qkv, const float* dout, float* dqkv, int N
   const float scale = 1.0f / sqrtf((float)head_dim);
 #define ADM_ATTB_CASE(DD)                                                                                   \
   if (head_dim == DD) {                                                                                     \
+    set_last_attention_variant(ATT_BWD, DD);                                                                \
     ADM_LAUNCH((attn_bwd_kernel<DD>), dim3(heads, N), dim3(bs), smem, st, qkv, dout, dqkv, C, T, scale);     \
     return ADM_CHECK_LAUNCH();                                                                              \
   }

@@ -152,6 +152,7 @@ int launch_cross_attention(const float* q, const float* ctx, const float* Wk, co
   const float scale = 1.0f / sqrtf((float)head_dim);
 #define ADM_XATT_CASE(DD)                                                                                         \
   if (head_dim == DD) {                                                                                           \
+    set_last_attention_variant(ATT_CROSS, DD);                                                                    \
     ADM_LAUNCH((cross_attention_kernel<DD>), grid, block, smem, st, q, ctx, Wk, Wv, out, C, T, S, Dc, scale);     \
     return ADM_CHECK_LAUNCH();                                                                                    \
   }
@@ -228,6 +229,7 @@ int launch_attention_blocked(const float* qkv, float* out, int N, int C, int T, 
   const float scale = 1.0f / sqrtf((float)head_dim);
 #define ADM_ATTB_CASE(DD)                                                                          \
   if (head_dim == DD) {                                                                            \
+    set_last_attention_variant(ATT_BLOCKED, DD);                                                   \
     ADM_LAUNCH((attention_blocked_kernel<DD>), grid, block, smem, st, qkv, out, C, T, KB, scale);  \
     return ADM_CHECK_LAUNCH();                                                                     \
   }
@@ -376,6 +378,7 @@ int launch_attention_mfma(const float* qkv, float* out, int N, int C, int T, int
   const float scale = 1.0f / sqrtf((float)head_dim);
 #define ADM_ATTM_CASE(DD)                                                                                        \
   if (head_dim == DD) {                                                                                          \
+    set_last_attention_variant(ATT_MFMA, DD);                                                                    \
     ADM_LAUNCH((attention_mfma_kernel<DD>), grid, block, smem, st, qkv, out, C, T, scale);                       \
     return ADM_CHECK_LAUNCH();                                                                                   \
   }
@@ -471,6 +474,20 @@ int launch_geglu_bwd(const float* in, const float* dy, float* din, int N, int C4
   return ADM_CHECK_LAUNCH();
 }
 
+// a * b rounded to fp32 before anything else uses it. Written as `a * scale - m` the logit is contracted into one fma on the device, so at
+// the row maximum the exponent is the product's rounding residual and not 0, and with one key p = exp(+-1e-6), dq = 1e-6 instead of exactly 0
+// (the toolchain's __fmul_rn is a plain product and is contracted like one; the pragma takes the `contract` flag off this product alone).
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#if defined(ADM_EMU)
+  return __fmul_rn(a, b);
+#else
+  {
+#pragma clang fp contract(off)
+    return a * b;
+  }
+#endif
+}
+
 // Cross-attention backward: dq (N, C, T) and the gradients of to_k / to_v (C, Dc) (accumulated with atomics: every
 // (sample, head) workgroup owns D rows of each, the batch sums over samples). The encoding itself is data (no gradient).
 // One workgroup per (head, sample); K, V recomputed into LDS; lanes stride over the tokens; dK / dV of the head
@@ -510,14 +527,14 @@ __global__ void __launch_bounds__(256) cross_attention_bwd_kernel(const float* _
       float a = 0.f;
       ADM_UNROLL
       for (int d = 0; d < D; ++d) a = fmaf(qv[d], Ks[s * D + d], a);
-      m = fmaxf(m, a * scale);
+      m = fmaxf(m, mul_rounded(a, scale));
     }
     float l = 0.f, dsum = 0.f;
     for (int s = 0; s < S; ++s) {
       float a = 0.f, gv = 0.f;
       ADM_UNROLL
       for (int d = 0; d < D; ++d) { a = fmaf(qv[d], Ks[s * D + d], a); gv = fmaf(go[d], Vs[s * D + d], gv); }
-      const float p = __expf(a * scale - m);
+      const float p = __expf(mul_rounded(a, scale) - m);
       l += p; dsum = fmaf(p, gv, dsum);
     }
     const float inv = 1.0f / l, Di = dsum * inv;
@@ -525,7 +542,7 @@ __global__ void __launch_bounds__(256) cross_attention_bwd_kernel(const float* _
       float a = 0.f, gv = 0.f;
       ADM_UNROLL
       for (int d = 0; d < D; ++d) { a = fmaf(qv[d], Ks[s * D + d], a); gv = fmaf(go[d], Vs[s * D + d], gv); }
-      const float p = __expf(a * scale - m) * inv;
+      const float p = __expf(mul_rounded(a, scale) - m) * inv;
       const float ds = p * (gv - Di) * scale;
       ADM_UNROLL
       for (int d = 0; d < D; ++d) {
@@ -559,6 +576,7 @@ int launch_cross_attention_bwd(const float* q, const float* ctx, const float* Wk
   const float scale = 1.0f / sqrtf((float)head_dim);
 #define ADM_XATTB_CASE(DD)                                                                                              \
   if (head_dim == DD) {                                                                                                 \
+    set_last_attention_variant(ATT_CROSS_BWD, DD);                                                                      \
     ADM_LAUNCH((cross_attention_bwd_kernel<DD>), dim3(heads, N), dim3(bs), smem, st, q, ctx, Wk, Wv, dy, dq, dWk, dWv, C, \
                T, S, Dc, scale);                                                                                        \
     return ADM_CHECK_LAUNCH();                                                                                          \
@@ -590,9 +608,10 @@ __global__ void __launch_bounds__(256) attn_bwd_blocked_dq_kernel(const float* _
   float q[D], go[D], dq[D];
   ADM_UNROLL
   for (int d = 0; d < D; ++d) { q[d] = live ? qb[(long)d * T + i] : 0.f; go[d] = live ? ob[(long)d * T + i] : 0.f; dq[d] = 0.f; }
-  float m = -3.0e38f, l = 0.f, dsum = 0.f;
+  float m = -3.0e38f;
+  double l = 0.0, dsum = 0.0;                        // in double, as in attn_bwd_kernel (k_backward.hip): dq is a cancellation against D_i = dsum / l
   for (int pass = 0; pass < 2; ++pass) {
-    const float inv = pass ? 1.0f / l : 0.f, Di = pass ? dsum * inv : 0.f;
+    const float inv = pass ? (float)(1.0 / l) : 0.f, Di = pass ? (float)(dsum / l) : 0.f;
     for (int j0 = 0; j0 < T; j0 += KB) {
       const int nb = T - j0 < KB ? T - j0 : KB;
       __syncthreads();
@@ -610,14 +629,14 @@ __global__ void __launch_bounds__(256) attn_bwd_blocked_dq_kernel(const float* _
           for (int d = 0; d < D; ++d) s = fmaf(q[d], Ks[j * D + d], s);
           bm = fmaxf(bm, s * scale);
         }
-        const float corr = __expf(m - bm);
+        const double corr = (double)__expf(m - bm);
         l *= corr; dsum *= corr; m = bm;
         for (int j = 0; j < nb; ++j) {
           float s = 0.f, gv = 0.f;
           ADM_UNROLL
           for (int d = 0; d < D; ++d) { s = fmaf(q[d], Ks[j * D + d], s); gv = fmaf(go[d], Vs[j * D + d], gv); }
           const float pj = __expf(s * scale - m);
-          l += pj; dsum = fmaf(pj, gv, dsum);
+          l += (double)pj; dsum = fma((double)pj, (double)gv, dsum);
         }
       } else {
         for (int j = 0; j < nb; ++j) {
@@ -636,7 +655,7 @@ __global__ void __launch_bounds__(256) attn_bwd_blocked_dq_kernel(const float* _
   ADM_UNROLL
   for (int d = 0; d < D; ++d) dqb[(long)d * T + i] = dq[d];
   float* sp = stats + 3 * (((long)n * heads + head) * T + i);
-  sp[0] = m; sp[1] = 1.0f / l; sp[2] = dsum / l;
+  sp[0] = m; sp[1] = (float)(1.0 / l); sp[2] = (float)(dsum / l);
 }
 
 template <int D>
@@ -698,6 +717,7 @@ int launch_attention_bwd_blocked(const float* qkv, const float* dout, float* dqk
   const float scale = 1.0f / sqrtf((float)head_dim);
 #define ADM_ATTBB_CASE(DD)                                                                                                  \
   if (head_dim == DD) {                                                                                                     \
+    set_last_attention_variant(ATT_BWD_BLOCKED, DD);                                                                        \
     ADM_LAUNCH((attn_bwd_blocked_dq_kernel<DD>), grid, dim3(bs), smem, st, qkv, dout, dqkv, stats, C, T, KB, scale);          \
     ADM_LAUNCH((attn_bwd_blocked_dkv_kernel<DD>), grid, dim3(bs), smem, st, qkv, dout, dqkv, (const float*)stats, C, T, KB,   \
                scale);                                                                                                      \

@@ -68,7 +68,7 @@ int adm_has_experiments(void);
  *   on a second stream beside those ops (scheduling only: bit-identical results; adm_plan_op.hoist_from shows where) | 0 every op in list
  *   order on the caller's stream | -1 ADM_SIDE_OVERLAP. Every net re-plans on its next call (a UNet's captured loop is re-captured).
  * The dispatch epoch moves only when a value really changes; set options BEFORE adm_unet_refresh_weights / the next train step.
- * adm_version() = 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
+ * adm_version() = 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
 int adm_set_option(const char* name, int value);
 /* Per-(device, stream) scratch the library keeps for a stream (the split-K slab buffer of the small-plane convolutions, >= 1 MiB, at most
  * 1024 streams per device): give it back BEFORE destroying a stream that has run library calls. Drains the stream first (a captured graph of
@@ -76,6 +76,14 @@ int adm_set_option(const char* name, int value);
 int adm_release_stream(void* stream);
 /* Kernel variant the last adm_conv2d on this thread dispatched to (see adm_op_profile.variant; 4311 = Winograd). */
 int adm_last_conv_variant(void);
+/* Kernel family the last attention entry point on this thread launched (adm_version() >= 106; tests assert the dispatch rules with it):
+ * family * 100 + head_dim, families 1 = one pass, whole head in LDS (attention_kernel) | 2 = four lanes per query (attention_split4_kernel,
+ * "single_sample") | 3 = key blocks, online softmax on the vector ALUs (attention_blocked_kernel) | 4 = flash form on the f32 MFMAs
+ * (attention_mfma_kernel) | 5 = adm_cross_attention | 6 = adm_attention_backward (head resident in LDS) | 7 = adm_attention_backward_blocked |
+ * 8 = adm_cross_attention_backward. E.g. 108 = attention_kernel<8>, 432 = attention_mfma_kernel<32>. 0 before the first launch; a call that
+ * returns an error before launching (an LDS slab that does not fit, an unsupported head_dim) leaves the value as it was. The executors'
+ * attention ops (adm_unet_forward, adm_unet_forward_backward) go through the same launchers and report the same way. */
+int adm_last_attention_variant(void);
 
 /* ---------------------------------------------------------------- scheduler epilogue (rows S2,S3,P4,P5)
  * One fused elementwise kernel replacing DDIMScheduler.step / DDPMScheduler.step
