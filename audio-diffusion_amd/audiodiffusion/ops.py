@@ -437,3 +437,31 @@ def conv_small_cout_backward(x, w, dy, gn=None, act=False):
                                                  N.ptr(gn[1]) if gn else None, int(act), N.ptr(w), N.ptr(dy), Co,
                                                  N.ptr(da), N.ptr(dW), N.stream_for(x)))
     return da, dW
+
+
+# ---------------------------------------------------------------------------------------------- timestep embedding (test aids)
+def time_embedding(t, freqs, w1, b1, w2, b2, flip=True, save=False):
+    """t (B,), freqs (dim_in / 2,), linear_1 (dim_emb, dim_in), linear_2 (dim_emb, dim_emb) -> (emb, emb_act) (B, dim_emb) each, emb_act = silu(emb);
+    save=True: also (sinusoid (B, dim_in), z (B, dim_emb)), the input and the pre-activation output of linear_1."""
+    for a in (t, freqs, w1, b1, w2, b2):
+        _f32(a)
+    B, half = t.numel(), freqs.numel()
+    dim_emb, dim_in = w1.shape
+    assert dim_in == 2 * half and tuple(w2.shape) == (dim_emb, dim_emb)
+    emb = torch.empty((B, dim_emb), dtype=torch.float32, device=t.device)
+    emb_act = torch.empty_like(emb)
+    sinus = torch.empty((B, dim_in), dtype=torch.float32, device=t.device) if save else None
+    z = torch.empty_like(emb) if save else None
+    N.check(N.lib().adm_time_embedding(N.ptr(t), N.ptr(freqs), half, int(flip), N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), dim_in, dim_emb,
+                                       N.ptr(emb), B, N.ptr(sinus), N.ptr(z), N.ptr(emb_act), N.stream_for(t)))
+    return (emb, emb_act, sinus, z) if save else (emb, emb_act)
+
+
+def temb_proj(emb, w, bias, activated=False):
+    """(B, K) x stacked time_emb_proj weights (R, K) -> bias + silu(emb) W^T (B, R); activated=True: emb already holds silu(emb)."""
+    _f32(emb), _f32(w), _f32(bias)
+    B, K = emb.shape
+    R = w.shape[0]
+    out = torch.empty((B, R), dtype=torch.float32, device=emb.device)
+    N.check(N.lib().adm_temb_proj(N.ptr(emb), N.ptr(w), N.ptr(bias), N.ptr(out), B, K, R, int(activated), N.stream_for(emb)))
+    return out

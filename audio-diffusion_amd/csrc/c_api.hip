@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 106; }   // 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 107; }   // 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -125,6 +125,23 @@ int adm_groupnorm_stats(const float* x1, int C1, const float* x2, int C2, int N,
                         const float* gamma, const float* beta, float* scale, float* shift, void* stream) {
   ADM_REQUIRE(x1 && gamma && beta && scale && shift, "groupnorm_stats: null argument");
   return launch_groupnorm_stats(x1, C1, x2, C2, N, HW, groups, eps, gamma, beta, scale, shift, (hipStream_t)stream);
+}
+
+// Test aids (adm_version() >= 107): the two launches of the timestep-embedding path, which the executors call with their own shapes only.
+int adm_time_embedding(const float* t_dev, const float* freqs, int half_dim, int flip, const float* w1, const float* b1, const float* w2,
+                       const float* b2, int dim_in, int dim_emb, float* emb, int B, float* save_sinus, float* save_z, float* emb_act,
+                       void* stream) {
+  ADM_REQUIRE(t_dev && freqs && w1 && b1 && w2 && b2 && emb, "time_embedding: null argument");
+  ADM_REQUIRE(B > 0 && half_dim > 0 && dim_in == 2 * half_dim && dim_emb > 0, "time_embedding: dim_in = 2 * half_dim, B and dim_emb positive");
+  return launch_time_embedding(t_dev, 1, nullptr, nullptr, freqs, half_dim, flip, w1, b1, w2, b2, dim_in, dim_emb, emb, B,
+                               (hipStream_t)stream, save_sinus, save_z, emb_act);
+}
+
+int adm_temb_proj(const float* emb, const float* w, const float* bias, float* out, int B, int K, int R, int emb_is_activated,
+                  void* stream) {
+  ADM_REQUIRE(emb && w && bias && out, "temb_proj: null argument");
+  ADM_REQUIRE(B > 0 && K > 0 && R > 0, "temb_proj: B, K and R positive");
+  return launch_temb_proj(emb, w, bias, out, B, K, R, (hipStream_t)stream, emb_is_activated ? 1 : 0);
 }
 
 int adm_conv_stats_tiles(const adm_conv_args* a) { return a ? conv_stats_tiles(*a) : 0; }

@@ -15,6 +15,9 @@ namespace adm {
 // y[n][c][t] = (x[n][c][t] - mean_t) * rstd_t * gamma[c] + beta[c], statistics over c for every token (n, t).
 // One lane per token, channel loop strided by T (coalesced across lanes); mean then centred variance (two passes, as
 // ATen's LayerNorm kernel), then the write pass: 3 reads + 1 write of 4 B per element.
+// The two sums over C are kept in double, here and in the tile and backward kernels below: serial fp32 sums over 320 .. 1280 channels of
+// tokens whose mean is 30 standard deviations from zero put y 10 - 19x and dgamma 17x above torch fp32's own error
+// (tests/test_norm_sweep.py, profiles/norm_accuracy.md); the kernels are HBM bound, one conversion and one f64 operation per element.
 __global__ void __launch_bounds__(256) layernorm_nct_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ y, int C,
                                                             long T, float eps) {
@@ -22,12 +25,12 @@ __global__ void __launch_bounds__(256) layernorm_nct_kernel(const float* __restr
   if (t >= T) return;
   const float* xp = x + (long)blockIdx.y * C * T + t;
   float* yp = y + (long)blockIdx.y * C * T + t;
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += xp[(long)c * T];
-  const float mean = s / (float)C;
-  float v = 0.f;
-  for (int c = 0; c < C; ++c) { const float d = xp[(long)c * T] - mean; v = fmaf(d, d, v); }
-  const float rstd = rsqrtf(v / (float)C + eps);
+  double s = 0.0;
+  for (int c = 0; c < C; ++c) s += (double)xp[(long)c * T];
+  const float mean = (float)(s / (double)C);
+  double v = 0.0;
+  for (int c = 0; c < C; ++c) { const float d = xp[(long)c * T] - mean; v = fma((double)d, (double)d, v); }
+  const float rstd = (float)(1.0 / sqrt(v / (double)C + (double)eps));
   for (int c = 0; c < C; ++c) yp[(long)c * T] = (xp[(long)c * T] - mean) * rstd * gamma[c] + beta[c];
 }
 
@@ -39,23 +42,23 @@ __global__ void __launch_bounds__(256) layernorm_nct_kernel(const float* __restr
 __global__ void __launch_bounds__(256) layernorm_nct_tile_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float* __restrict__ y, int C,
                                                                  long T, float eps) {
-  __shared__ float red[2][4][64];
+  __shared__ double red[2][4][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long t = (long)blockIdx.x * 64 + lane;
   const float* xp = x + (long)blockIdx.y * C * T + t;
   float* yp = y + (long)blockIdx.y * C * T + t;
-  float s = 0.f;
+  double s = 0.0;
   _Pragma("unroll 8")
-  for (int c = w; c < C; c += 4) s += xp[(long)c * T];
+  for (int c = w; c < C; c += 4) s += (double)xp[(long)c * T];
   red[0][w][lane] = s;
   __syncthreads();
-  const float mean = ((red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane])) / (float)C;
-  float v = 0.f;
+  const float mean = (float)(((red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane])) / (double)C);
+  double v = 0.0;
   _Pragma("unroll 8")
-  for (int c = w; c < C; c += 4) { const float d = xp[(long)c * T] - mean; v = fmaf(d, d, v); }
+  for (int c = w; c < C; c += 4) { const float d = xp[(long)c * T] - mean; v = fma((double)d, (double)d, v); }
   red[1][w][lane] = v;
   __syncthreads();
-  const float rstd = rsqrtf(((red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane])) / (float)C + eps);
+  const float rstd = (float)(1.0 / sqrt(((red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane])) / (double)C + (double)eps));
   _Pragma("unroll 8")
   for (int c = w; c < C; c += 4) yp[(long)c * T] = (xp[(long)c * T] - mean) * rstd * gamma[c] + beta[c];
 }
@@ -401,18 +404,18 @@ __global__ void __launch_bounds__(256) layernorm_nct_bwd_dx_kernel(const float* 
   const long base = (long)blockIdx.y * C * T + t;
   const float* xp = x + base;
   const float* gp = dy + base;
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += xp[(long)c * T];
-  const float mean = s / (float)C;
-  float v = 0.f;
-  for (int c = 0; c < C; ++c) { const float d = xp[(long)c * T] - mean; v = fmaf(d, d, v); }
-  const float rstd = rsqrtf(v / (float)C + eps);
-  float s1 = 0.f, s2 = 0.f;
+  double s = 0.0;
+  for (int c = 0; c < C; ++c) s += (double)xp[(long)c * T];
+  const float mean = (float)(s / (double)C);
+  double v = 0.0;
+  for (int c = 0; c < C; ++c) { const float d = xp[(long)c * T] - mean; v = fma((double)d, (double)d, v); }
+  const float rstd = (float)(1.0 / sqrt(v / (double)C + (double)eps));
+  double a1 = 0.0, a2 = 0.0;
   for (int c = 0; c < C; ++c) {
     const float g = gp[(long)c * T] * gamma[c], xh = (xp[(long)c * T] - mean) * rstd;
-    s1 += g; s2 = fmaf(g, xh, s2);
+    a1 += (double)g; a2 = fma((double)g, (double)xh, a2);
   }
-  s1 /= (float)C; s2 /= (float)C;
+  const float s1 = (float)(a1 / (double)C), s2 = (float)(a2 / (double)C);
   float* dp = dx + base;
   for (int c = 0; c < C; ++c) {
     const float g = gp[(long)c * T] * gamma[c], xh = (xp[(long)c * T] - mean) * rstd;
@@ -426,15 +429,15 @@ __global__ void __launch_bounds__(256) layernorm_nct_bwd_dx_kernel(const float* 
 __global__ void __launch_bounds__(256) layernorm_nct_bwd_affine_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                        const float* __restrict__ stats, float* dgamma,
                                                                        float* dbeta, int N, int C, long T) {
-  __shared__ float red[2][256];
+  __shared__ double red[2][256];
   const int c = blockIdx.x, tid = threadIdx.x;
-  float a = 0.f, b = 0.f;
+  double a = 0.0, b = 0.0;
   for (long i = tid; i < (long)N * T; i += 256) {
     const long n = i / T, t = i - n * T;
     const long e = (n * C + c) * T + t;
     const float g = dy[e];
-    a = fmaf(g, (x[e] - stats[2 * i]) * stats[2 * i + 1], a);
-    b += g;
+    a = fma((double)g, (double)((x[e] - stats[2 * i]) * stats[2 * i + 1]), a);
+    b += (double)g;
   }
   red[0][tid] = a; red[1][tid] = b;
   __syncthreads();
@@ -442,7 +445,7 @@ __global__ void __launch_bounds__(256) layernorm_nct_bwd_affine_kernel(const flo
     if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
     __syncthreads();
   }
-  if (tid == 0) { dgamma[c] += red[0][0]; dbeta[c] += red[1][0]; }
+  if (tid == 0) { dgamma[c] += (float)red[0][0]; dbeta[c] += (float)red[1][0]; }
 }
 
 int launch_layernorm_nct_bwd(const float* x, const float* dy, const float* gamma, float* dx, int accumulate, float* stats,

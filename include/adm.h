@@ -68,7 +68,7 @@ int adm_has_experiments(void);
  *   on a second stream beside those ops (scheduling only: bit-identical results; adm_plan_op.hoist_from shows where) | 0 every op in list
  *   order on the caller's stream | -1 ADM_SIDE_OVERLAP. Every net re-plans on its next call (a UNet's captured loop is re-captured).
  * The dispatch epoch moves only when a value really changes; set options BEFORE adm_unet_refresh_weights / the next train step.
- * adm_version() = 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
+ * adm_version() = 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
 int adm_set_option(const char* name, int value);
 /* Per-(device, stream) scratch the library keeps for a stream (the split-K slab buffer of the small-plane convolutions, >= 1 MiB, at most
  * 1024 streams per device): give it back BEFORE destroying a stream that has run library calls. Drains the stream first (a captured graph of
@@ -84,6 +84,20 @@ int adm_last_conv_variant(void);
  * returns an error before launching (an LDS slab that does not fit, an unsupported head_dim) leaves the value as it was. The executors'
  * attention ops (adm_unet_forward, adm_unet_forward_backward) go through the same launchers and report the same way. */
 int adm_last_attention_variant(void);
+
+/* Test aids (adm_version() >= 107): the two launches of the timestep-embedding path at shapes of the caller's choice (the executors run
+ * them at their model's shapes only).
+ *   adm_time_embedding: emb (B, dim_emb) = linear_2(silu(linear_1(sinusoid(t)))) with sinusoid = [cos | sin](t[b] * freqs[i]) when flip, else
+ *     [sin | cos]; t (B) and freqs (half_dim) on the device, dim_in = 2 * half_dim, w1 (dim_emb, dim_in), w2 (dim_emb, dim_emb).
+ *     NULL or written: save_sinus (B, dim_in) the input of linear_1, save_z (B, dim_emb) its pre-activation output, emb_act (B, dim_emb) =
+ *     silu(emb).
+ *   adm_temb_proj: out (B, R) = bias + silu(emb) W^T with w (R, K) the stacked time_emb_proj matrices, emb (B, K); emb_is_activated != 0:
+ *     `emb` already holds silu(emb) (adm_time_embedding's emb_act). K <= 1536 when B >= 8. */
+int adm_time_embedding(const float* t_dev, const float* freqs, int half_dim, int flip, const float* w1, const float* b1, const float* w2,
+                       const float* b2, int dim_in, int dim_emb, float* emb, int B, float* save_sinus, float* save_z, float* emb_act,
+                       void* stream);
+int adm_temb_proj(const float* emb, const float* w, const float* bias, float* out, int B, int K, int R, int emb_is_activated,
+                  void* stream);
 
 /* ---------------------------------------------------------------- scheduler epilogue (rows S2,S3,P4,P5)
  * One fused elementwise kernel replacing DDIMScheduler.step / DDPMScheduler.step
