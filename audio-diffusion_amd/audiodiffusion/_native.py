@@ -41,6 +41,10 @@ class ConvArgs(C.Structure):
     ]
 
 
+class WgradVariant(C.Structure):       # include/adm.h: adm_wgrad_variant
+    _fields_ = [("kernel", C.c_int), ("reduce", C.c_int), ("split", C.c_int), ("tiles_per_block", C.c_int)]
+
+
 class OpProfile(C.Structure):
     _fields_ = [("kind", C.c_int), ("variant", C.c_int), ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -144,6 +148,8 @@ _OPTIONAL_SIGS = {
     "adm_groupnorm_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "adm_conv_wgrad_workspace": (_l, [C.POINTER(ConvArgs)]),
     "adm_conv2d_wgrad": (_i, [C.POINTER(ConvArgs), _vp, _vp, _i, _vp, _vp]),
+    "adm_last_wgrad_variant": (_i, [C.POINTER(WgradVariant)]),
+    "adm_wgrad_reduce": (_i, [_vp, _i, _l, _vp, _i, _i, _vp]),
     "adm_blocked_image_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "adm_blocked_sums_scratch": (_l, [_i, _i, _i, _i]),
     "adm_blocked_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),

@@ -325,15 +325,52 @@ def groupnorm_backward(x1, da, mean_rstd, gamma, beta, groups, act, x2=None):
     return dx1, dx2, dg, db
 
 
-def conv2d_wgrad(x1, dy, Cout, ks, x2=None, up=False, stride=1, pad_lo=1, gn=None, act=False):
-    """dW (Cout,Cin,ks,ks) of the fused conv, with the load-path activation recomputed."""
-    _f32(x1), _f32(dy)
+def _batch_view(t, bstride):
+    """Address and batch stride of a source given as a slice of a wider (N, C + extra, H, W) buffer: every sample contiguous, samples `bstride`
+    floats apart (adm_conv_args.x1_bstride / x2_bstride)."""
+    assert t.stride(0) == bstride and t[0].is_contiguous() and bstride >= t[0].numel(), "a batch-strided source: contiguous samples, stride(0) = bstride"
+    assert t.is_cuda == N.is_device_build()
+    return C.c_void_p(t.data_ptr())
+
+
+def conv2d_wgrad(x1, dy, Cout, ks, x2=None, up=False, stride=1, pad_lo=1, gn=None, act=False, accumulate=False, out=None,
+                 x1_bstride=None, x2_bstride=None):
+    """dW (Cout,Cin,ks,ks) of the fused conv, with the load-path activation recomputed.
+    out: the caller's dW (a contiguous view of Cout*Cin*ks*ks floats at any float offset of a gradient buffer) instead of a fresh tensor;
+    accumulate: dW += instead of dW =; x1_bstride / x2_bstride: x1 / x2 are channel slices of wider buffers (samples that many floats apart)."""
+    _f32(x1 if x1_bstride is None else x1[:1]), _f32(dy)
     Ct = x1.shape[1] + (x2.shape[1] if x2 is not None else 0)
-    a = _conv_args(x1, dy, None, ks, x2, up, stride, pad_lo, gn, act, Cout)  # wpacked unused by wgrad
+    a = _conv_args(x1 if x1_bstride is None else x1[:1], dy, None, ks, None if x2_bstride is not None else x2, up, stride, pad_lo, gn, act,
+                   Cout)  # wpacked unused by wgrad
+    a.N = x1.shape[0]
+    if x1_bstride is not None:
+        a.x1, a.x1_bstride = _batch_view(x1, x1_bstride), x1_bstride
+    if x2_bstride is not None:
+        a.x2, a.C2, a.x2_bstride = _batch_view(x2, x2_bstride), x2.shape[1], x2_bstride
     ws_n = N.lib().adm_conv_wgrad_workspace(C.byref(a))
     ws = torch.empty(ws_n, dtype=torch.float32, device=x1.device)
-    dW = torch.zeros((Cout, Ct, ks, ks), dtype=torch.float32, device=x1.device)
-    N.check(N.lib().adm_conv2d_wgrad(C.byref(a), N.ptr(dy), N.ptr(dW), 0, N.ptr(ws), N.stream_for(x1)))
+    if out is None:
+        dW = torch.zeros((Cout, Ct, ks, ks), dtype=torch.float32, device=x1.device)
+    else:
+        _f32(out)
+        assert out.numel() == Cout * Ct * ks * ks and out.device == x1.device
+        dW = out
+    N.check(N.lib().adm_conv2d_wgrad(C.byref(a), N.ptr(dy), N.ptr(dW), int(accumulate), N.ptr(ws), N.stream_for(x1)))
+    return dW
+
+
+def last_wgrad_variant():
+    """(kernel, reduce, split, tiles_per_block) of the last conv2d_wgrad on this thread (include/adm.h: adm_last_wgrad_variant)."""
+    v = N.WgradVariant()
+    N.lib().adm_last_wgrad_variant(C.byref(v))
+    return v.kernel, v.reduce, v.split, v.tiles_per_block
+
+
+def wgrad_reduce(workspace, split, numel, dW, accumulate=False, taps=1):
+    """dW (=|+=) the sum of the `split` slabs of `numel` floats in `workspace` ([tap][cout*cin] order -> (cout, cin, tap)): adm_wgrad_reduce."""
+    _f32(workspace), _f32(dW)
+    assert workspace.numel() >= split * numel and dW.numel() == numel
+    N.check(N.lib().adm_wgrad_reduce(N.ptr(workspace), split, numel, N.ptr(dW), int(accumulate), taps, N.stream_for(dW)))
     return dW
 
 
@@ -419,20 +456,29 @@ def linear_backward(dY, X, W, x_silu=False):
     return dW, db, dX
 
 
-def conv_small_cin_wgrad(x, dy):
+def conv_small_cin_wgrad(x, dy, out=None):
+    """out: the caller's dW (Cout*Cin*9 floats); the kernel ADDS to what it holds."""
     Nn, Ci, H, W = x.shape
     Co = dy.shape[1]
-    dW = torch.zeros((Co, Ci, 3, 3), device=x.device)
+    dW = torch.zeros((Co, Ci, 3, 3), device=x.device) if out is None else out
+    assert dW.numel() == Co * Ci * 9
     N.check(N.lib().adm_conv_small_cin_wgrad(N.ptr(x), Ci, Nn, H, W, N.ptr(dy), Co, N.ptr(dW), N.stream_for(x)))
     return dW
 
 
-def conv_small_cout_backward(x, w, dy, gn=None, act=False):
-    """conv_out class (Cout <= 4): returns (da, dW) with da the gradient w.r.t. the activated input."""
+def conv_small_cout_backward(x, w, dy, gn=None, act=False, out=None, want=(True, True)):
+    """conv_out class (Cout <= 4): returns (da, dW) with da the gradient w.r.t. the activated input.
+    out = (da, dW): the caller's destinations (either None: a fresh one); da is written, dW is ADDED to. want = (da?, dW?): False passes NULL."""
     Nn, Ci, H, W = x.shape
     Co = dy.shape[1]
-    da = torch.empty_like(x)
-    dW = torch.zeros((Co, Ci, 3, 3), device=x.device)
+    da, dW = out if out is not None else (None, None)
+    if want[0] and da is None:
+        da = torch.empty_like(x)
+    if want[1] and dW is None:
+        dW = torch.zeros((Co, Ci, 3, 3), device=x.device)
+    da, dW = (da if want[0] else None), (dW if want[1] else None)
+    assert da is None or da.numel() == x.numel()
+    assert dW is None or dW.numel() == Co * Ci * 9
     N.check(N.lib().adm_conv_small_cout_backward(N.ptr(x), Ci, Nn, H, W, N.ptr(gn[0]) if gn else None,
                                                  N.ptr(gn[1]) if gn else None, int(act), N.ptr(w), N.ptr(dy), Co,
                                                  N.ptr(da), N.ptr(dW), N.stream_for(x)))

@@ -76,6 +76,12 @@ int launch_pack_winograd_weight(const float* w, float* wu, int Cout, int Cin, hi
 int launch_pack_winograd_weight_T(const float* w, float* wu, int Cout, int Cin, hipStream_t st);  // data-gradient filters
 bool winograd_enabled();
 void set_wgrad_max_split(int v);  // k_conv_wgrad.hip
+void set_wgrad_path(int v);       // k_conv_wgrad.hip: option "wgrad_path" (0 heuristic | 1 no eight-wave | 2 no pipelined | 3 generic kernels only)
+// what the last launch_conv_wgrad on this thread ran (include/adm.h: adm_wgrad_variant has the encoding)
+enum { WG_GEN_3_1 = 310, WG_GEN_3_2 = 320, WG_GEN_1_1 = 110, WG_PF3 = 1300, WG_PF3_FAST = 1301, WG_PF1 = 1100, WG_PF1_FAST = 1101,
+       WG_SP = 2304, WG_SP8 = 2308, WG_BF16_3X3 = 5316, WG_BF16_1X1 = 5116 };
+struct WgradVariant { int kernel, reduce, split, tiles_per_block; };
+WgradVariant last_wgrad_variant();
 void bump_dispatch_epoch();        // net_exec.hip: a process-wide option changed -> training nets re-learn which packings they read
 unsigned dispatch_epoch();
 void set_blk_direct_dy(int v);     // net_exec.hip: option "blk_direct_dy" (read when a training plan is made)

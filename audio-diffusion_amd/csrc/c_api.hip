@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 107; }   // 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 108; }   // 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -48,7 +48,7 @@ const char* adm_last_error(void) { return adm::last_error(); }
 int adm_set_option(const char* name, int value) {
   ADM_REQUIRE(name, "set_option: null name");
   const std::string nm(name);
-  static const char* known[] = {"conv_wino", "wino_pair", "wino5", "wino6", "single_sample", "wgrad_max_split", "conv_bf16", "conv_op16_f16", "blk_direct_dy", "gn_fuse_finish", "side_overlap"};
+  static const char* known[] = {"conv_wino", "wino_pair", "wino5", "wino6", "single_sample", "wgrad_max_split", "wgrad_path", "conv_bf16", "conv_op16_f16", "blk_direct_dy", "gn_fuse_finish", "side_overlap"};
   bool ok = false;
   for (const char* k : known) ok |= nm == k;
   if (!ok) ADM_FAIL(std::string("set_option: unknown option ") + name);
@@ -62,6 +62,9 @@ int adm_set_option(const char* name, int value) {
                 "set_option: wino6 takes -1 (environment), 0 (off), 1 (default layer rule), 2 (every layer the kernel tiles) or a plane-size floor n >= 16");
   if (nm == "single_sample") ADM_REQUIRE(value >= -1 && value <= 1, "set_option: single_sample takes -1 (environment), 0 (off) or 1 (on)");
   if (nm == "side_overlap") ADM_REQUIRE(value >= -1 && value <= 1, "set_option: side_overlap takes -1 (environment), 0 (off) or 1 (on)");
+  if (nm == "wgrad_path")
+    ADM_REQUIRE(value >= 0 && value <= 3, "set_option: wgrad_path takes 0 (heuristic), 1 (no eight-wave kernel), 2 (no software-pipelined kernels) or "
+                "3 (generic kernels only)");
   static std::mutex mu;
   static std::map<std::string, int> last;
   {
@@ -77,6 +80,7 @@ int adm_set_option(const char* name, int value) {
   if (nm == "single_sample") { adm::set_single_sample(value); return 0; }
   if (nm == "wino_pair") { adm::set_winograd_pair(value); return 0; }
   if (nm == "wgrad_max_split") { adm::set_wgrad_max_split(value); return 0; }
+  if (nm == "wgrad_path") { adm::set_wgrad_path(value); return 0; }
   if (nm == "conv_bf16") { adm::set_conv_bf16(value); return 0; }
   if (nm == "conv_op16_f16") { adm::set_conv_op16_f16(value); return 0; }
   if (nm == "gn_fuse_finish") { adm::set_gn_fuse_finish(value); return 0; }

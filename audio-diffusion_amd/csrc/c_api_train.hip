@@ -29,6 +29,18 @@ int adm_conv2d_wgrad(const adm_conv_args* a, const float* dy, float* dW, int acc
   return launch_conv_wgrad(*a, dy, dW, accumulate, workspace, (hipStream_t)stream);
 }
 
+int adm_last_wgrad_variant(adm_wgrad_variant* out) {
+  const WgradVariant v = last_wgrad_variant();
+  if (out) { out->kernel = v.kernel; out->reduce = v.reduce; out->split = v.split; out->tiles_per_block = v.tiles_per_block; }
+  return v.kernel;
+}
+
+int adm_wgrad_reduce(const float* workspace, int split, long numel, float* dW, int accumulate, int taps, void* stream) {
+  ADM_REQUIRE(workspace && dW, "wgrad_reduce: null argument");
+  ADM_REQUIRE(split >= 1 && numel >= 1 && taps >= 1 && numel % taps == 0, "wgrad_reduce: split, numel and taps positive, numel a multiple of taps");
+  return launch_wgrad_reduce(workspace, split, numel, dW, accumulate, taps, (hipStream_t)stream);
+}
+
 size_t adm_blocked_image_bytes(int N, int C, int H, int W) { return blk_image_bytes(N, C, H, W); }
 long adm_blocked_sums_scratch(int N, int C, int H, int W) { return blk_sums_scratch(N, C, H, W); }
 int adm_blocked_apply(const float* x1, int C1, const float* x2, int C2, int N, int H, int W, const float* scale,

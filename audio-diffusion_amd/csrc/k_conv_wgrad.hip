@@ -851,7 +851,12 @@ __global__ void __launch_bounds__(256) wgrad_reduce9_kernel(const float* __restr
 
 static inline int ilog2w(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
+// what the last weight-gradient launch on this thread ran (include/adm.h: adm_last_wgrad_variant; tests assert the dispatch rule with it)
+static thread_local WgradVariant g_last_wgrad = {0, 0, 0, 0};
+WgradVariant last_wgrad_variant() { return g_last_wgrad; }
+
 int launch_wgrad_reduce(const float* workspace, int split, long numel, float* dW, int accumulate, int taps, hipStream_t st) {
+  g_last_wgrad.reduce = taps == 9 ? 9 : 1;
   if (taps == 9) {
     const long M = numel / 9;
     long g = (M + 63) / 64;
@@ -868,6 +873,10 @@ int launch_wgrad_reduce(const float* workspace, int split, long numel, float* dW
 // workspace floats needed by launch_conv_wgrad for this shape
 static int g_wgrad_max_split = 0;   // 0 = no cap; adm_set_option("wgrad_max_split", n) caps the split-K factor (tests use it
 void set_wgrad_max_split(int v) { g_wgrad_max_split = v; }   // to put several pixel tiles on one workgroup)
+// adm_set_option("wgrad_path", v): 0 = the heuristic below | 1 = no eight-wave kernel | 2 = no software-pipelined kernels | 3 = generic
+// kernels only. Under 0 the developer A/B switches ADM_WGRAD_SP8 / ADM_WGRAD_SP / ADM_WGRAD_PF (=0) still say the same three things.
+static int g_wgrad_path = 0;
+void set_wgrad_path(int v) { g_wgrad_path = v; }
 
 long conv_wgrad_workspace(const adm_conv_args& a, int* split_out) {
   const int C2 = a.x2 ? a.C2 : 0, Ct = a.C1 + C2;
@@ -936,20 +945,26 @@ int launch_conv_wgrad(const adm_conv_args& a, const float* dy, float* dW, int ac
   }();
   (void)once;
 #endif
-  static const int use_pf = [] { const char* e = getenv("ADM_WGRAD_PF"); return e ? atoi(e) : 1; }();
+  static const int env_pf = [] { const char* e = getenv("ADM_WGRAD_PF"); return e ? atoi(e) : 1; }();
+  static const int env_sp = [] { const char* e = getenv("ADM_WGRAD_SP"); return e ? atoi(e) : 1; }();
+  static const int env_sp8 = [] { const char* e = getenv("ADM_WGRAD_SP8"); return e ? atoi(e) : 1; }();
+  const int path = g_wgrad_path;
+  const int use_pf = path >= 3 ? 0 : env_pf, use_sp = path >= 2 ? 0 : env_sp, use_sp8 = path >= 1 ? 0 : env_sp8;
+  auto record = [&](int kernel, int split) { g_last_wgrad.kernel = kernel; g_last_wgrad.split = split; g_last_wgrad.tiles_per_block = p.tiles_per_block; };
   const int PE = NI * p.IH * p.IW;
   if (conv_bf16_mode() >= 2 && conv1x1_wgrad_bf16_eligible(a)) {   // level 2: 1x1 weight gradient on bf16 operands
     const int slabs = launch_conv1x1_wgrad_bf16(a, dy, workspace, p.split, st);
     ADM_REQUIRE(slabs > 0 && slabs <= p.split, "conv1x1_wgrad_bf16: launch failed");
+    record(WG_BF16_1X1, slabs);
     return launch_wgrad_reduce(workspace, slabs, numel, dW, accumulate, a.ks * a.ks, st);
   }
   if (conv_bf16_enabled() && conv_wgrad_bf16_eligible(a)) {   // mixed precision: bf16 operands, fp32 partial sums
     ADM_TRY(launch_conv_wgrad_bf16(a, dy, dW, accumulate, workspace, p.split, st));
+    record(WG_BF16_3X3, p.split);
     return launch_wgrad_reduce(workspace, p.split, numel, dW, accumulate, a.ks * a.ks, st);
   }
   // tile-invariant prefetch path: no upsample fold, every channel chunk inside one source tensor, full cout tiles
   const bool fast = a.up == 0 && a.C1 % CB == 0 && Ct % CB == 0 && a.Cout % 128 == 0;
-  static const int use_sp = [] { const char* e = getenv("ADM_WGRAD_SP"); return e ? atoi(e) : 1; }();
   if (use_pf && use_sp && fast && a.stride == 1 && a.ks == 3 && TW == 16 && TH == 4) {
     const size_t smem_sp = sizeof(float) * (2 * ((size_t)64 * 129 + (size_t)CB * 109) + 256);
 #if !defined(ADM_EMU)
@@ -959,7 +974,6 @@ int launch_conv_wgrad(const adm_conv_args& a, const float* dy, float* dW, int ac
     }();
     (void)once_sp;
 #endif
-    static const int use_sp8 = [] { const char* e = getenv("ADM_WGRAD_SP8"); return e ? atoi(e) : 1; }();
     if (use_sp8) {
 #if !defined(ADM_EMU)
       static bool once_sp8 = [] {
@@ -969,18 +983,24 @@ int launch_conv_wgrad(const adm_conv_args& a, const float* dy, float* dW, int ac
       (void)once_sp8;
 #endif
       ADM_LAUNCH(conv_wgrad_sp8_kernel, grid, dim3(512), smem_sp + sizeof(float) * 256, st, p);
+      record(WG_SP8, p.split);
     } else {
       ADM_LAUNCH(conv_wgrad_sp_kernel, grid, block, smem_sp, st, p);
+      record(WG_SP, p.split);
     }
   } else if (use_pf && a.stride == 1 && a.ks == 3 && PE <= 128) {
     if (fast) ADM_LAUNCH((conv_wgrad_pf_kernel<3, true>), grid, block, smem, st, p);
     else ADM_LAUNCH((conv_wgrad_pf_kernel<3, false>), grid, block, smem, st, p);
+    record(fast ? WG_PF3_FAST : WG_PF3, p.split);
   } else if (use_pf && a.ks == 1) {
     if (fast) ADM_LAUNCH((conv_wgrad_pf_kernel<1, true>), grid, block, smem, st, p);
     else ADM_LAUNCH((conv_wgrad_pf_kernel<1, false>), grid, block, smem, st, p);
+    record(fast ? WG_PF1_FAST : WG_PF1, p.split);
   } else if (a.ks == 3 && a.stride == 1) {
     ADM_LAUNCH((conv_wgrad_kernel<3, 1>), grid, block, smem, st, p);
+    record(WG_GEN_3_1, p.split);
   } else if (a.ks == 3) {
+    record(WG_GEN_3_2, p.split);
 #if !defined(ADM_EMU)
     static const bool want_prof = getenv("ADM_WGRAD_PROF") != nullptr;
     if (want_prof) {        // developer aid: per-phase cycle accounting of the generic stride-2 kernel, printed after the launch
@@ -1002,6 +1022,7 @@ int launch_conv_wgrad(const adm_conv_args& a, const float* dy, float* dW, int ac
     ADM_LAUNCH((conv_wgrad_kernel<3, 2>), grid, block, smem, st, p);
   } else {
     ADM_LAUNCH((conv_wgrad_kernel<1, 1>), grid, block, smem, st, p);
+    record(WG_GEN_1_1, p.split);
   }
   return launch_wgrad_reduce(workspace, p.split, numel, dW, accumulate, a.ks * a.ks, st);
 }

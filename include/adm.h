@@ -53,6 +53,8 @@ int adm_has_experiments(void);
  * "wino_pair": accepted and ignored since round 6 (conv_wino4_kernel keeps one cadence: one workgroup barrier per two chunks);
  * "wgrad_max_split" = n caps the split-K factor of adm_conv2d_wgrad (0 = heuristic; tests use it to put several pixel tiles on
  *   one workgroup);
+ * "wgrad_path" = 0 (default) | 1 | 2 | 3 keeps adm_conv2d_wgrad off its eight-wave / software-pipelined / prefetch kernels (tests reach every
+ *   kernel with it; see adm_last_wgrad_variant below);
  * "conv_bf16" = 1 runs eligible 3x3 stride-1 convolutions (forward, data gradient and weight gradient) on 16-bit MFMA operands
  *   with fp32 accumulation (`--mixed_precision bf16`, scripts/train_unet.py:391-401), 2 = additionally the eligible 1x1 convolutions
  *   and stride-2 data gradients, 0 = fp32 everywhere (default), -1 = back to the ADM_CONV_BF16 environment variable;
@@ -68,7 +70,7 @@ int adm_has_experiments(void);
  *   on a second stream beside those ops (scheduling only: bit-identical results; adm_plan_op.hoist_from shows where) | 0 every op in list
  *   order on the caller's stream | -1 ADM_SIDE_OVERLAP. Every net re-plans on its next call (a UNet's captured loop is re-captured).
  * The dispatch epoch moves only when a value really changes; set options BEFORE adm_unet_refresh_weights / the next train step.
- * adm_version() = 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
+ * adm_version() = 108 (option "wgrad_path", test aids adm_last_wgrad_variant, adm_wgrad_reduce); 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
 int adm_set_option(const char* name, int value);
 /* Per-(device, stream) scratch the library keeps for a stream (the split-K slab buffer of the small-plane convolutions, >= 1 MiB, at most
  * 1024 streams per device): give it back BEFORE destroying a stream that has run library calls. Drains the stream first (a captured graph of
@@ -437,6 +439,26 @@ int adm_groupnorm_backward(const float* x1, int C1, const float* x2, int C2, con
  * output gradient dy; split-K partial slabs live in `workspace` (adm_conv_wgrad_workspace floats). */
 long adm_conv_wgrad_workspace(const adm_conv_args* a);
 int adm_conv2d_wgrad(const adm_conv_args* a, const float* dy, float* dW, int accumulate, float* workspace, void* stream);
+/* Test aids (adm_version() >= 108).
+ * adm_last_wgrad_variant: what the last adm_conv2d_wgrad on this thread launched (returns `kernel`; `out` NULL or filled). The executors'
+ * weight gradients go through the same launcher and report the same way. All zero before the first launch; a call that fails before it
+ * launches leaves the values as they were.
+ *   kernel: 310 / 320 / 110 = generic conv_wgrad_kernel<3,1> / <3,2> / <1,1> | 1300 / 1301 = conv_wgrad_pf_kernel<3,false> / <3,true> and
+ *     1100 / 1101 = <1,false> / <1,true> (register prefetch; the last digit is the tile-invariant fast path) | 2304 = conv_wgrad_sp_kernel
+ *     (four waves, LDS double buffer) | 2308 = conv_wgrad_sp8_kernel (eight waves) | 5316 / 5116 = the bf16-operand routes of option
+ *     "conv_bf16" (3x3 / 1x1; tiles_per_block is then the fp32 launcher's figure, not theirs);
+ *   reduce: 1 = wgrad_reduce_kernel, 9 = wgrad_reduce9_kernel (adm_wgrad_reduce sets this field too);
+ *   split, tiles_per_block: the number of partial-sum slabs that were reduced and the pixel tiles per workgroup
+ *     (tiles_per_block = ceil(n_ptiles / split0), split = ceil(n_ptiles / tiles_per_block), split0 = min(ceil(768 / (cout tiles x channel
+ *     chunks)), "wgrad_max_split", n_ptiles)).
+ * Option "wgrad_path" (adm_set_option) = 0 (default): the launcher's heuristic, where the developer switches ADM_WGRAD_SP8=0 / ADM_WGRAD_SP=0 /
+ *   ADM_WGRAD_PF=0 of the environment still mean what 1 / 2 / 3 mean here | 1 no eight-wave kernel | 2 no software-pipelined kernels (the
+ *   prefetch kernels take their shapes) | 3 generic kernels only. Any other value is an error and is not recorded.
+ * adm_wgrad_reduce: the launcher's second launch alone: dW (=|+=) sum over k < split of workspace[k][0:numel], slabs in [tap][cout*cin] order,
+ *   dW in (cout, cin, tap) order; taps == 9 runs wgrad_reduce9_kernel, anything else wgrad_reduce_kernel. numel % taps == 0. */
+typedef struct adm_wgrad_variant { int kernel, reduce, split, tiles_per_block; } adm_wgrad_variant;
+int adm_last_wgrad_variant(adm_wgrad_variant* out);
+int adm_wgrad_reduce(const float* workspace, int split, long numel, float* dW, int accumulate, int taps, void* stream);
 /* ---- blocked 16-bit operand images (option "conv_bf16" = 3; `--mixed_precision bf16`, scripts/train_unet.py:391-401) ----
  * A blocked image is  img[n][C/8][H+2][W+2] x 16 B : one 16-byte unit = 8 consecutive channels of one pixel as bf16 (or IEEE
  * binary16 under option "conv_op16_f16"), with a one-pixel halo that must be ZERO (zero the buffer once after allocating it:
@@ -494,7 +516,8 @@ int adm_attention_backward(const float* qkv, const float* dout, float* dqkv, int
 /* Linear Y = act(X) W^T + b: dW (J,K) += dY^T act(X), db += colsum(dY), dX = (dY W) * act'(X); x_silu: act = SiLU. */
 int adm_linear_backward(const float* dY, int ldy, const float* X, const float* W, int B, int J, int K, int x_silu,
                         float* dW, float* db, float* dX, void* stream);
-/* conv_in (Cin <= 4) weight gradient and conv_out (Cout <= 4) weight + data gradient (the direct small-channel kernels). */
+/* conv_in (Cin <= 4) weight gradient and conv_out (Cout <= 4) weight + data gradient (the direct small-channel kernels). Both ADD to
+ * what dW holds (fp32 atomics over the samples): zero it, or pass the gradient to accumulate onto; da is written; da or dW may be NULL. */
 int adm_conv_small_cin_wgrad(const float* x, int Cin, int N, int H, int W, const float* dy, int Cout, float* dW,
                              void* stream);
 int adm_conv_small_cout_backward(const float* x, int Cin, int N, int H, int W, const float* gn_scale,
