@@ -86,6 +86,7 @@ _SIGS = {
     "adm_has_experiments": (C.c_int, []),
     "adm_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "adm_sched_step": (C.c_int, [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
+    "adm_sched_multistep": (C.c_int, [C.c_void_p] * 5 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
     "adm_add_noise": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                 C.c_int, C.c_int, C.c_long, C.c_void_p]),
     "adm_dequant_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
@@ -133,6 +134,8 @@ _SIGS = {
     "adm_vae_plan_ops": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(PlanOp), C.c_int, C.POINTER(C.c_int)]),
     "adm_sample_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "adm_sample_loop_multistep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), c_float_p, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "adm_encode_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_int, C.c_void_p]),
 }
 # entry points added by later translation units (k_mel.hip); bound when present in the header AND the library

@@ -34,6 +34,22 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
     return out
 
 
+def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
+                    u8_out=None, step_dev=None):
+    """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_multistep_kernel`). x, eps, hist: (B,C,H,W); k_hist_table: (n,) fp32
+    beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev: optional
+    int32 device scalar that replaces `step`."""
+    _f32(x), _f32(eps), _f32(hist), _f32(k_hist_table)
+    assert hist.shape == x.shape and k_hist_table.numel() == coef_table.shape[0]
+    B, Cc, H, W = x.shape
+    out = torch.empty_like(x) if out is None else out
+    n_mask = mask.shape[1] if mask is not None else 0
+    N.check(N.lib().adm_sched_multistep(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
+                                        N.ptr(k_hist_table), N.ptr(hist), N.ptr(step_dev), int(step), N.ptr(mask), n_mask,
+                                        int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x)))
+    return out
+
+
 def add_noise(x0, noise, sa, sb, per_sample):
     """scheduler.add_noise. per_sample=True: x0,noise (B,...) with sa,sb (B,) -> (B,...).
     per_sample=False (mask build, pipeline:157): x0 (1,H,W) broadcast, noise (B,1,H,W), sa,sb (n,) -> (B,n,H,W)."""

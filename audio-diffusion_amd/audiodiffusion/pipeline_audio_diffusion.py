@@ -27,7 +27,7 @@ from PIL import Image
 from . import _native as N
 from . import ops
 from .mel import Mel
-from .schedulers import DDIMScheduler, DDPMScheduler, randn_tensor
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, randn_tensor
 from .unet import UNet2DConditionModel, UNet2DModel
 from .vae import AutoencoderKL
 
@@ -38,7 +38,8 @@ class PipelineOutput(dict):
 
 
 _CLASSES = {"AutoencoderKL": AutoencoderKL, "UNet2DModel": UNet2DModel, "UNet2DConditionModel": UNet2DConditionModel,
-            "DDIMScheduler": DDIMScheduler, "DDPMScheduler": DDPMScheduler, "Mel": Mel}
+            "DDIMScheduler": DDIMScheduler, "DDPMScheduler": DDPMScheduler,
+            "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler, "Mel": Mel}
 
 
 class DiffusionPipeline:
@@ -50,6 +51,11 @@ class DiffusionPipeline:
         self._modules = {}
         self._progress_bar_config = {}
         self._device = N.default_device()
+
+    def __setattr__(self, name, value):
+        if name in self.__dict__.get("_modules", ()):   # `pipe.scheduler = other`: the registered component follows (save_pretrained)
+            self._modules[name] = value
+        super().__setattr__(name, value)
 
     def register_modules(self, **kwargs):
         for k, v in kwargs.items():
@@ -128,7 +134,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         vqvae: AutoencoderKL for latent audio diffusion or None
         unet: UNet2DModel
         mel: Mel — transform audio <-> spectrogram
-        scheduler: DDIMScheduler or DDPMScheduler
+        scheduler: DDIMScheduler, DDPMScheduler or DPMSolverMultistepScheduler
     """
 
     _optional_components = ["vqvae"]
@@ -140,6 +146,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         self.register_modules(unet=unet, scheduler=scheduler, mel=mel, vqvae=vqvae)
 
     def get_default_steps(self) -> int:
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            return 20   # (the reference's rule would say 1000: pointless for a solver built for few steps)
         return 50 if isinstance(self.scheduler, DDIMScheduler) else 1000
 
     # ---- the native denoising loop (pipeline_audio_diffusion.py:159-185 + :192-194) ----------------------
@@ -148,7 +156,9 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
         before that step index, so that a single step of a long schedule can be compared in isolation."""
         sched, unet = self.scheduler, self.unet
-        rows = sched.coef_rows(eta)[start_step:stop_step]
+        multistep = isinstance(sched, DPMSolverMultistepScheduler)
+        # (a multistep run that starts late starts first order: its rows depend on where it starts, not only on the slice)
+        rows = sched.loop_rows(start_step, stop_step) if multistep else sched.coef_rows(eta)[start_step:stop_step]
         n = len(rows)
         x = images.contiguous().clone()  # the reference never writes the loop state back into `noise`
         B, Cc, H, W = x.shape
@@ -187,9 +197,15 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 # (B, n_total, H, W): this chunk starts at row `done`; the kernel indexes mask[:, step_in_chunk]
                 mask_chunk = mask[:, done:done + m].contiguous()
                 mask_ptr = N.ptr(mask_chunk)
-            N.check(N.lib().adm_sample_loop(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start), int(mask_end),
-                                            N.ptr(u8) if (last and u8 is not None) else None, int(use_graph),
-                                            N.stream_for(x)))
+            u8_ptr = N.ptr(u8) if (last and u8 is not None) else None
+            if multistep:   # no noise, so no chunking: the history of the previous x0 lives inside this one native call
+                assert m == n
+                khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
+                N.check(N.lib().adm_sample_loop_multistep(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
+                                                          int(mask_end), u8_ptr, int(use_graph), N.stream_for(x)))
+            else:
+                N.check(N.lib().adm_sample_loop(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start), int(mask_end),
+                                                u8_ptr, int(use_graph), N.stream_for(x)))
             if x.is_cuda and (noise_ptr is not None or mask_ptr is not None) and not last:
                 torch.cuda.current_stream(x.device).synchronize()  # staging buffers are rewritten next chunk
             done += m

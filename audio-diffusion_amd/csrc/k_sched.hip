@@ -2,6 +2,9 @@
 // Replaces DDIMScheduler.step / DDPMScheduler.step + mask overwrite + final dequant
 // (reference: audiodiffusion/pipeline_audio_diffusion.py:165-185,192-194; SURVEY.md §8(a) S2-S4,P4,P5).
 // One float4 per lane per iteration, grid-stride; algorithmic bytes: 12 B/elem (x, eps in; out) +4 with noise.
+// sched_multistep_kernel is the same epilogue for the second-order multistep solver (DPM-Solver++ 2M): the update is linear in
+// (x, x0 of this step, x0 of the previous step), so it adds one per-step coefficient k_hist and one per-element history buffer that the
+// same lane reads and rewrites in place: +8 B/elem over sched_step_kernel (one history read, one history write), 20 B/elem in all.
 #include "adm_kernels.h"
 
 namespace adm {
@@ -38,6 +41,64 @@ __global__ void __launch_bounds__(256) sched_step_kernel(
     if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
     float r[4] = {sched_one(xv.x, ev.x, nv.x, c), sched_one(xv.y, ev.y, nv.y, c), sched_one(xv.z, ev.z, nv.z, c),
                   sched_one(xv.w, ev.w, nv.w, c)};
+    if (mask != nullptr) {
+      const long e0 = i * 4;
+      const long b = e0 / per_sample;
+      const long p = e0 - b * per_sample;  // C == 1: p = row*W + col
+      const int col0 = (int)(p % W);
+      const float* mrow = mask + b * mask_bstride + (long)s * per_sample + p;
+      ADM_UNROLL
+      for (int k = 0; k < 4; ++k) {
+        const int col = col0 + k;
+        if (col < mask_start || col >= W - mask_end) r[k] = mrow[k];
+      }
+    }
+    reinterpret_cast<float4*>(out)[i] = make_float4(r[0], r[1], r[2], r[3]);
+    if (u8 != nullptr) {
+      const unsigned q = (unsigned)quant_u8(r[0]) | ((unsigned)quant_u8(r[1]) << 8) |
+                         ((unsigned)quant_u8(r[2]) << 16) | ((unsigned)quant_u8(r[3]) << 24);
+      reinterpret_cast<unsigned*>(u8)[i] = q;
+    }
+  }
+}
+
+// Multistep data-prediction update: m0 = x0 of this step (clipped as in sched_one), m1 = x0 of the previous step from `hist`;
+//   prev = k_x0*m0 + k_x*x + k_hist*m1 (+ k_noise*noise);  hist = m0 (always, and before the mask: the history is the model's x0).
+// hist is read ONLY where k_hist != 0: the first row of a run has k_hist == 0 and finds the buffer uninitialised (0 * NaN must not
+// reach the output). out may alias x; each lane reads and rewrites its own elements of hist.
+__global__ void __launch_bounds__(256) sched_multistep_kernel(
+    const float* x, const float* __restrict__ eps, const float* noise, float* out, float* hist, unsigned char* u8,
+    const adm_sched_coef* __restrict__ table, const float* __restrict__ k_hist_table, const int* __restrict__ step_dev,
+    int step, const float* __restrict__ mask, long mask_bstride, int mask_start, int mask_end, int W, long per_sample,
+    long n4, long noise_step_stride, int u8_step) {
+  const int s = step_dev ? *step_dev : step;
+  const adm_sched_coef c = table[s];
+  const float k_hist = k_hist_table[s];
+  const bool use_hist = k_hist != 0.f;
+  const bool use_noise = noise != nullptr && c.k_noise != 0.f;
+  noise += (long)s * noise_step_stride;
+  if (u8_step >= 0 && s != u8_step) u8 = nullptr;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 xv = reinterpret_cast<const float4*>(x)[i];
+    const float4 ev = reinterpret_cast<const float4*>(eps)[i];
+    float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
+    if (use_hist) hv = reinterpret_cast<const float4*>(hist)[i];
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, ns[4] = {nv.x, nv.y, nv.z, nv.w},
+                hs[4] = {hv.x, hv.y, hv.z, hv.w};
+    float r[4], m[4];
+    ADM_UNROLL
+    for (int k = 0; k < 4; ++k) {
+      float m0 = (xs[k] - c.sqrt_beta * es[k]) / c.sqrt_alpha;
+      if (c.clip >= 0.f) m0 = fminf(fmaxf(m0, -c.clip), c.clip);
+      float prev = c.k_x0 * m0 + c.k_x * xs[k];
+      if (use_hist) prev = prev + k_hist * hs[k];
+      if (use_noise) prev = prev + c.k_noise * ns[k];
+      m[k] = m0;
+      r[k] = prev;
+    }
+    reinterpret_cast<float4*>(hist)[i] = make_float4(m[0], m[1], m[2], m[3]);
     if (mask != nullptr) {
       const long e0 = i * 4;
       const long b = e0 / per_sample;
@@ -128,6 +189,19 @@ int launch_sched_step(const float* x, const float* eps, const float* noise, floa
                       int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, hipStream_t st) {
   return launch_sched_step_loop(x, eps, noise, 0, out, u8, -1, table, step_dev, step, mask, n_mask_steps, mask_start,
                                 mask_end, B, C, H, W, st);
+}
+
+int launch_sched_multistep(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
+                           float* hist, uint8_t* u8, int u8_step, const adm_sched_coef* table, const float* k_hist_table,
+                           const int* step_dev, int step, const float* mask, int n_mask_steps, int mask_start,
+                           int mask_end, int B, int C, int H, int W, hipStream_t st) {
+  const long per_sample = (long)C * H * W, n = per_sample * B;
+  ADM_REQUIRE(W % 4 == 0, "sched_multistep: W must be a multiple of 4");
+  ADM_REQUIRE(mask == nullptr || C == 1, "sched_multistep: mask path requires C == 1 (as in the reference)");
+  ADM_LAUNCH(sched_multistep_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, eps, noise, out, hist, u8, table,
+             k_hist_table, step_dev, step, mask, (long)n_mask_steps * per_sample, mask_start, mask_end, W, per_sample, n / 4,
+             noise_step_stride, u8_step);
+  return ADM_CHECK_LAUNCH();
 }
 
 int launch_step_advance(int* step_dev, hipStream_t st) {

@@ -36,8 +36,11 @@ struct adm_unet {
   std::vector<void*> extra;  // per-batch buffers besides the net arena
   PackItem* temb_items = nullptr; int n_temb_items = 0;   // restack_temb's device table
   float *emb = nullptr, *emb_act = nullptr, *temb_all = nullptr, *t_dev = nullptr, *eps_buf = nullptr;
+  float* hist_buf = nullptr;     // x0 of the previous step (multistep scheduler loop); same size as eps_buf
   adm_sched_coef* coef_dev = nullptr;
   int coef_cap = 0;
+  float* khist_dev = nullptr;    // per-step history coefficient of the multistep loop, beside coef_dev
+  int khist_cap = 0;
   int* step_dev = nullptr;
   // training
   bool training = false;
@@ -282,6 +285,8 @@ static int plan(adm_unet* h, int B) {
   ADM_TRY(extra_alloc(h, (void**)&h->t_dev, sizeof(float) * (size_t)B));
   ADM_TRY(extra_alloc(h, (void**)&h->eps_buf,
                       sizeof(float) * (size_t)B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
+  ADM_TRY(extra_alloc(h, (void**)&h->hist_buf,
+                      sizeof(float) * (size_t)B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
   ADM_TRY(extra_alloc(h, (void**)&h->step_dev, sizeof(int)));
   if (h->training) {
     ADM_TRY(extra_alloc(h, (void**)&h->dtemb_all, sizeof(float) * (size_t)B * h->temb_rows));
@@ -321,9 +326,19 @@ static int ensure_coef(adm_unet* h, const adm_sched_coef* coef_host, int n, hipS
   return 0;
 }
 
+static int ensure_khist(adm_unet* h, const float* k_hist_host, int n, hipStream_t st) {
+  if (h->khist_cap < n) {
+    ADM_TRY(dalloc(h, (void**)&h->khist_dev, sizeof(float) * (size_t)n));
+    h->khist_cap = n;
+  }
+  return copy_h2d(h->khist_dev, k_hist_host, sizeof(float) * (size_t)n, st);
+}
+
+enum { LOOP_SAMPLE = 0, LOOP_ENCODE = 1, LOOP_MULTISTEP = 2 };   // which step kernel follows the forward
+
 struct LoopArgs {
   float* x; int B; int n_steps; const float* step_noise; const float* mask; int mask_start, mask_end;
-  uint8_t* u8; int encode;
+  uint8_t* u8; int mode; const float* k_hist_host;
 };
 
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
@@ -332,8 +347,12 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
   const adm_sched_coef* table = h->coef_dev;
   ADM_TRY(run_forward(h, a.x, h->eps_buf, a.B, table, st));
   const long n = (long)a.B * c.in_channels * c.sample_h * c.sample_w;
-  if (a.encode) {
+  if (a.mode == LOOP_ENCODE) {
     ADM_TRY(launch_encode_step(a.x, h->eps_buf, table, h->step_dev, step, n, st));
+  } else if (a.mode == LOOP_MULTISTEP) {
+    ADM_TRY(launch_sched_multistep(a.x, h->eps_buf, a.step_noise, n, a.x, h->hist_buf, a.u8, a.n_steps - 1, table,
+                                   h->khist_dev, h->step_dev, step, a.mask, a.n_steps, a.mask_start, a.mask_end, a.B,
+                                   c.in_channels, c.sample_h, c.sample_w, st));
   } else {
     ADM_TRY(launch_sched_step_loop(a.x, h->eps_buf, a.step_noise, n, a.x, a.u8, a.n_steps - 1, table, h->step_dev, step,
                                    a.mask, a.n_steps, a.mask_start, a.mask_end, a.B, c.in_channels, c.sample_h,
@@ -350,6 +369,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
 #if defined(ADM_EMU)
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
+  if (a.mode == LOOP_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
   for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
   return 0;
 #else
@@ -363,13 +383,15 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
     ADM_HIP_OK(hipStreamWaitEvent(run, ev, 0));
   }
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, run));
+  if (a.mode == LOOP_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
   if (!use_graph) {
     for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
   } else {
     std::vector<uint64_t> key = {(uint64_t)a.x, (uint64_t)a.B, (uint64_t)a.n_steps, (uint64_t)a.step_noise,
                                  (uint64_t)a.mask, (uint64_t)a.mask_start, (uint64_t)a.mask_end, (uint64_t)a.u8,
-                                 (uint64_t)a.encode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
+                                 (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
                                  (uint64_t)h->net.ctx_S};
+    if (a.mode == LOOP_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
         // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
@@ -638,7 +660,20 @@ int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_h
                     const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out,
                     int use_graph, void* stream) {
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop: bad argument");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, 0};
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_SAMPLE, nullptr};
+  Bf16Scope fp32(0);
+  ADM_TRY(finalize(h));
+  InferenceScope inf(&h->net, (hipStream_t)stream);
+  ADM_TRY(inf.rc);
+  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+}
+
+int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host,
+                              int n_steps, const float* step_noise, const float* mask, int mask_start, int mask_end,
+                              uint8_t* u8_out, int use_graph, void* stream) {
+  ADM_REQUIRE(h && x && coef_host && k_hist_host && n_steps > 0, "sample_loop_multistep: bad argument");
+  ADM_REQUIRE(k_hist_host[0] == 0.f, "sample_loop_multistep: the first row of a run must be first order (k_hist[0] == 0)");
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_MULTISTEP, k_hist_host};
   Bf16Scope fp32(0);
   ADM_TRY(finalize(h));
   InferenceScope inf(&h->net, (hipStream_t)stream);
@@ -649,7 +684,7 @@ int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_h
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream) {
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "encode_loop: bad argument");
-  LoopArgs a{x, B, n_steps, nullptr, nullptr, 0, 0, nullptr, 1};
+  LoopArgs a{x, B, n_steps, nullptr, nullptr, 0, 0, nullptr, LOOP_ENCODE, nullptr};
   Bf16Scope fp32(0);
   ADM_TRY(finalize(h));
   InferenceScope inf(&h->net, (hipStream_t)stream);

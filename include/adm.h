@@ -123,6 +123,19 @@ int adm_sched_step(const float* x, const float* eps, const float* noise, float* 
                    const float* mask, int n_mask_steps, int mask_start, int mask_end,
                    int B, int C, int H, int W, void* stream);
 
+/* The same epilogue for a second-order multistep data-prediction solver (DPM-Solver++ 2M; adm_version() >= 109). The update is
+ * linear in (x, x0 of this step, x0 of the previous step), so adm_sched_coef keeps its eight fields and the one extra per-step
+ * coefficient travels beside it in k_hist_table (device, one float per row of coef_table):
+ *   m0   = clamp((x - sqrt_beta*eps) / sqrt_alpha, -clip, clip)
+ *   prev = k_x0*m0 + k_x*x + k_hist*hist + k_noise*noise;   hist = m0
+ * hist: (B,C,H,W) device buffer, read only where k_hist != 0 (it may be uninitialised on the first step of a run) and always
+ * written with m0, before the mask overwrite. Everything else as adm_sched_step; out may alias x. */
+int adm_sched_multistep(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
+                        const adm_sched_coef* coef_table, const float* k_hist_table, float* hist,
+                        const int* step_dev, int step,
+                        const float* mask, int n_mask_steps, int mask_start, int mask_end,
+                        int B, int C, int H, int W, void* stream);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -370,6 +383,12 @@ int adm_unet_set_grad_bucket_hook(adm_unet_t* h, int n_buckets, const long* boun
 int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                     const float* step_noise, const float* mask, int mask_start, int mask_end,
                     uint8_t* u8_out, int use_graph, void* stream);
+/* adm_sample_loop with the multistep epilogue (adm_sched_multistep; adm_version() >= 109). k_hist_host: n_steps floats (host),
+ * k_hist_host[0] must be 0 (the first row of a run is first order: the history buffer, which the handle owns and allocates with its
+ * plan, holds nothing of this run yet). coef_host[i].timestep feeds the time embedding as in adm_sample_loop. */
+int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host,
+                              int n_steps, const float* step_noise, const float* mask, int mask_start, int mask_end,
+                              uint8_t* u8_out, int use_graph, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
