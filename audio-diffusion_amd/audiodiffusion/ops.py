@@ -5,6 +5,7 @@ PyTorch/CPU fallback.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -22,14 +23,47 @@ def sched_coef_table(rows, device):
     return t.to(device)
 
 
-def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None):
-    """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194). x,eps: (B,C,H,W)."""
+def threshold_ranks(n, ratio):
+    """(lo, hi, w) of torch.quantile's linear interpolation over n elements, in the float32 arithmetic torch uses:
+    rank = float32(ratio) * float32(n - 1), the two neighbouring order statistics and the weight of the upper one."""
+    rank = np.float32(ratio) * np.float32(n - 1)
+    lo = np.floor(rank)
+    return int(lo), int(np.ceil(rank)), float(np.float32(rank - lo))
+
+
+def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None):
+    """Per-sample dynamic threshold s_b = clamp(quantile(|x0_b|, ratio), 1, max_value) of x0 = (x - sqrt_beta*eps) / sqrt_alpha
+    (csrc/k_sched.hip `sched_threshold_kernel`: an exact radix select on the device, equal to torch.quantile to the bit). -> (B,) fp32."""
+    _f32(x), _f32(eps)
+    B, Cc, H, W = x.shape
+    lo, hi, w = threshold_ranks(Cc * H * W, ratio)
+    out = torch.empty((B,), dtype=torch.float32, device=x.device) if out is None else out
+    N.check(N.lib().adm_sched_threshold(N.ptr(x), N.ptr(eps), N.ptr(coef_table), N.ptr(step_dev), int(step), lo, hi, w,
+                                        float(max_value), N.ptr(out), B, Cc, H, W, N.stream_for(x)))
+    return out
+
+
+def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
+               step_dev=None, scale_out=None):
+    """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194). x,eps: (B,C,H,W). threshold: None, or
+    (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it instead of the static
+    clamp (`adm_sched_step_thresholded`; scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device
+    scalar that replaces `step`."""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
     out = torch.empty_like(x) if out is None else out
     n_mask = mask.shape[1] if mask is not None else 0
+    if threshold is not None:
+        ratio, max_value = threshold
+        lo, hi, w = threshold_ranks(Cc * H * W, ratio)
+        scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+        N.check(N.lib().adm_sched_step_thresholded(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out),
+                                                   N.ptr(coef_table), N.ptr(step_dev), int(step), N.ptr(mask), n_mask,
+                                                   int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x), lo, hi, w,
+                                                   float(max_value), N.ptr(scale)))
+        return out
     N.check(N.lib().adm_sched_step(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
-                                   None, int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
+                                   N.ptr(step_dev), int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
                                    N.stream_for(x)))
     return out
 

@@ -157,6 +157,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         before that step index, so that a single step of a long schedule can be compared in isolation."""
         sched, unet = self.scheduler, self.unet
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
+        thresh = None if multistep else sched.threshold()
         # (a multistep run that starts late starts first order: its rows depend on where it starts, not only on the slice)
         rows = sched.loop_rows(start_step, stop_step) if multistep else sched.coef_rows(eta)[start_step:stop_step]
         n = len(rows)
@@ -203,6 +204,11 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
                 N.check(N.lib().adm_sample_loop_multistep(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
                                                           int(mask_end), u8_ptr, int(use_graph), N.stream_for(x)))
+            elif thresh is not None:   # dynamic thresholding: the statistic is over this tensor's C*H*W (the latent's, with a VAE)
+                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0])
+                N.check(N.lib().adm_sample_loop_thresholded(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start),
+                                                            int(mask_end), u8_ptr, int(use_graph), N.stream_for(x), lo, hi, w,
+                                                            thresh[1]))
             else:
                 N.check(N.lib().adm_sample_loop(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start), int(mask_end),
                                                 u8_ptr, int(use_graph), N.stream_for(x)))

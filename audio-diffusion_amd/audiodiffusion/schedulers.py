@@ -8,6 +8,8 @@ scalar reads. `coef_rows()` exports the whole coefficient table so the native sa
 (`adm_sample_loop`) can replay a captured hipGraph for every step. `DPMSolverMultistepScheduler` (second-order multistep,
 not used by the reference itself) goes through the sibling kernel and loop (`adm_sched_multistep`,
 `adm_sample_loop_multistep`): one more coefficient per step and a per-element history of the previous x0 prediction.
+`thresholding=True` (DDPM / DDIM) replaces the static clamp of x0 by the dynamic one: a per-sample percentile selected on the
+device (`adm_sched_threshold`) in front of the step kernel, in `step()` and inside the captured loop (`adm_sample_loop_thresholded`).
 """
 import json
 import math
@@ -53,7 +55,8 @@ class _SchedulerBase:
     _class_name = "SchedulerMixin"
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                      trained_betas=None, clip_sample=True, clip_sample_range=1.0, prediction_type="epsilon",
-                     timestep_spacing="leading", steps_offset=0, thresholding=False)
+                     timestep_spacing="leading", steps_offset=0, thresholding=False,
+                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0)
 
     def __init__(self, **kwargs):
         cfg = dict(self._defaults)
@@ -79,8 +82,11 @@ class _SchedulerBase:
             raise NotImplementedError("only prediction_type='epsilon' (what the reference trains) is implemented")
         if cfg["timestep_spacing"] != "leading":
             raise NotImplementedError("only timestep_spacing='leading' is implemented")
-        if cfg.get("thresholding"):
-            raise NotImplementedError("thresholding is not implemented")
+        # dynamic thresholding (Imagen §2.3; diffusers' `_threshold_sample` [3P-recall]): checked whether or not it is switched on
+        if not 0.0 <= float(cfg["dynamic_thresholding_ratio"]) <= 1.0:
+            raise ValueError(f"dynamic_thresholding_ratio={cfg['dynamic_thresholding_ratio']!r} must be in [0, 1]")
+        if not float(cfg["sample_max_value"]) >= 1.0:
+            raise ValueError(f"sample_max_value={cfg['sample_max_value']!r} must be >= 1")
 
     # ---- config (de)serialisation: scheduler/scheduler_config.json of the diffusers layout -------------
     @classmethod
@@ -157,6 +163,14 @@ class _SchedulerBase:
     def _clip(self):
         return float(self.config.clip_sample_range) if self.config.clip_sample else -1.0
 
+    def threshold(self):
+        """None, or (dynamic_thresholding_ratio, sample_max_value) when `thresholding` is on: x0 of every step is then clamped to
+        s = clamp(quantile(|x0|, ratio), 1, sample_max_value) per sample and divided by s, INSTEAD of the static `clip_sample`
+        clamp (diffusers' `if thresholding ... elif clip_sample`). With sample_max_value = 1 that is exactly the static clamp to 1."""
+        if not self.config.thresholding:
+            return None
+        return float(self.config.dynamic_thresholding_ratio), float(self.config.sample_max_value)
+
     def _step(self, model_output, timestep, sample, eta, generator, variance_noise):
         i = self._index_of(timestep)
         _, table, rows = self._cached(sample.device, eta)
@@ -164,7 +178,8 @@ class _SchedulerBase:
         if need_noise and variance_noise is None:
             variance_noise = randn_tensor(model_output.shape, generator, model_output.device, model_output.dtype)
         prev = ops.sched_step(sample.contiguous(), model_output.contiguous(), table, i,
-                              noise=variance_noise.contiguous() if variance_noise is not None else None)
+                              noise=variance_noise.contiguous() if variance_noise is not None else None,
+                              threshold=self.threshold())
         return SchedulerOutput(prev_sample=prev)
 
 
@@ -268,7 +283,8 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     once. Built: `solver_order` 1 and 2, `algorithm_type="dpmsolver++"`, `solver_type` midpoint / heun, the three timestep
     spacings, `final_sigmas_type` zero / sigma_min, `lower_order_final`, `euler_at_final`. Everything else raises
     NotImplementedError naming the key (the SDE variants need per-step noise and a history that survives the pipeline's
-    noise-staging chunks)."""
+    noise-staging chunks). `thresholding=True` raises as well: the selection kernel of the DDIM / DDPM schedulers
+    (`adm_sched_threshold`) is what a thresholded multistep kernel would reuse, but that sibling kernel is not built."""
     _class_name = "DPMSolverMultistepScheduler"
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
                      solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,

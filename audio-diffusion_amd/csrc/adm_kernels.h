@@ -14,6 +14,12 @@ int launch_sched_step_loop(const float* x, const float* eps, const float* noise,
                            const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
                            int W, hipStream_t st);
 int launch_step_advance(int* step_dev, hipStream_t st);
+int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
+                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st);
+int launch_sched_step_thresholded(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
+                                  uint8_t* u8, int u8_step, const adm_sched_coef* table, const int* step_dev, int step,
+                                  const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
+                                  int W, int lo, int hi, float w, float max_value, float* scale, hipStream_t st);
 int launch_sched_multistep(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
                            float* hist, uint8_t* u8, int u8_step, const adm_sched_coef* table, const float* k_hist_table,
                            const int* step_dev, int step, const float* mask, int n_mask_steps, int mask_start,

@@ -37,6 +37,7 @@ struct adm_unet {
   PackItem* temb_items = nullptr; int n_temb_items = 0;   // restack_temb's device table
   float *emb = nullptr, *emb_act = nullptr, *temb_all = nullptr, *t_dev = nullptr, *eps_buf = nullptr;
   float* hist_buf = nullptr;     // x0 of the previous step (multistep scheduler loop); same size as eps_buf
+  float* scale_buf = nullptr;    // per-sample dynamic threshold of the thresholded loop (B floats)
   adm_sched_coef* coef_dev = nullptr;
   int coef_cap = 0;
   float* khist_dev = nullptr;    // per-step history coefficient of the multistep loop, beside coef_dev
@@ -287,6 +288,7 @@ static int plan(adm_unet* h, int B) {
                       sizeof(float) * (size_t)B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
   ADM_TRY(extra_alloc(h, (void**)&h->hist_buf,
                       sizeof(float) * (size_t)B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
+  ADM_TRY(extra_alloc(h, (void**)&h->scale_buf, sizeof(float) * (size_t)B));
   ADM_TRY(extra_alloc(h, (void**)&h->step_dev, sizeof(int)));
   if (h->training) {
     ADM_TRY(extra_alloc(h, (void**)&h->dtemb_all, sizeof(float) * (size_t)B * h->temb_rows));
@@ -334,11 +336,12 @@ static int ensure_khist(adm_unet* h, const float* k_hist_host, int n, hipStream_
   return copy_h2d(h->khist_dev, k_hist_host, sizeof(float) * (size_t)n, st);
 }
 
-enum { LOOP_SAMPLE = 0, LOOP_ENCODE = 1, LOOP_MULTISTEP = 2 };   // which step kernel follows the forward
+enum { LOOP_SAMPLE = 0, LOOP_ENCODE = 1, LOOP_MULTISTEP = 2, LOOP_THRESH = 3 };   // which step kernel follows the forward
 
 struct LoopArgs {
   float* x; int B; int n_steps; const float* step_noise; const float* mask; int mask_start, mask_end;
   uint8_t* u8; int mode; const float* k_hist_host;
+  int th_lo = 0, th_hi = 0; float th_w = 0.f, th_max = 1.f;   // LOOP_THRESH: the two ranks, their weight and sample_max_value
 };
 
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
@@ -353,6 +356,10 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
     ADM_TRY(launch_sched_multistep(a.x, h->eps_buf, a.step_noise, n, a.x, h->hist_buf, a.u8, a.n_steps - 1, table,
                                    h->khist_dev, h->step_dev, step, a.mask, a.n_steps, a.mask_start, a.mask_end, a.B,
                                    c.in_channels, c.sample_h, c.sample_w, st));
+  } else if (a.mode == LOOP_THRESH) {
+    ADM_TRY(launch_sched_step_thresholded(a.x, h->eps_buf, a.step_noise, n, a.x, a.u8, a.n_steps - 1, table, h->step_dev, step,
+                                          a.mask, a.n_steps, a.mask_start, a.mask_end, a.B, c.in_channels, c.sample_h,
+                                          c.sample_w, a.th_lo, a.th_hi, a.th_w, a.th_max, h->scale_buf, st));
   } else {
     ADM_TRY(launch_sched_step_loop(a.x, h->eps_buf, a.step_noise, n, a.x, a.u8, a.n_steps - 1, table, h->step_dev, step,
                                    a.mask, a.n_steps, a.mask_start, a.mask_end, a.B, c.in_channels, c.sample_h,
@@ -392,6 +399,12 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
                                  (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
                                  (uint64_t)h->net.ctx_S};
     if (a.mode == LOOP_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
+    if (a.mode == LOOP_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
+      uint32_t wb, mb;
+      memcpy(&wb, &a.th_w, 4); memcpy(&mb, &a.th_max, 4);
+      key.push_back((uint64_t)h->scale_buf); key.push_back((uint64_t)a.th_lo); key.push_back((uint64_t)a.th_hi);
+      key.push_back(wb); key.push_back(mb);
+    }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
         // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
@@ -674,6 +687,19 @@ int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_co
   ADM_REQUIRE(h && x && coef_host && k_hist_host && n_steps > 0, "sample_loop_multistep: bad argument");
   ADM_REQUIRE(k_hist_host[0] == 0.f, "sample_loop_multistep: the first row of a run must be first order (k_hist[0] == 0)");
   LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_MULTISTEP, k_hist_host};
+  Bf16Scope fp32(0);
+  ADM_TRY(finalize(h));
+  InferenceScope inf(&h->net, (hipStream_t)stream);
+  ADM_TRY(inf.rc);
+  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+}
+
+int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
+                                const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out,
+                                int use_graph, void* stream, int lo, int hi, float w, float max_value) {
+  ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop_thresholded: bad argument");
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_THRESH, nullptr};
+  a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value;
   Bf16Scope fp32(0);
   ADM_TRY(finalize(h));
   InferenceScope inf(&h->net, (hipStream_t)stream);

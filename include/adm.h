@@ -136,6 +136,28 @@ int adm_sched_multistep(const float* x, const float* eps, const float* noise, fl
                         const float* mask, int n_mask_steps, int mask_start, int mask_end,
                         int B, int C, int H, int W, void* stream);
 
+/* Dynamic thresholding of the x0 prediction (Saharia et al. 2022, "Imagen" §2.3; diffusers' `thresholding`; adm_version() >= 110).
+ * Per sample b, with x0 = (x - sqrt_beta*eps) / sqrt_alpha as adm_sched_step computes it and n = C*H*W:
+ *   q_b = fma(w, b - a, a) if w < 0.5 else fma(-(b - a), 1 - w, b),  a, b = the order statistics of rank lo, hi of the ascending |x0_b|
+ *         (b - a and 1 - w rounded on their own, the multiply-add fused: torch's CPU lerp)
+ *   s_b = clamp(q_b, 1, max_value);   scale_out[b] = s_b   (B floats, device)
+ * which is torch.quantile(|x0_b|, ratio) (linear interpolation) to the bit when the caller computes, in float32,
+ *   rank = float32(ratio) * float32(n - 1), lo = floor(rank), hi = ceil(rank), w = rank - lo        (0 <= lo <= hi <= n - 1, hi - lo <= 1).
+ * One workgroup per sample, an exact MSB-first radix select over LDS histograms of the bit pattern of |x0| (integer counts only: a sample's
+ * result does not depend on the batch it sits in); x0 is recomputed from x and eps in every pass, nothing is kept in global memory, so the
+ * call needs no scratch. Non-finite x0 is out of contract for the value returned (NaN patterns order last); the call stays in bounds. */
+int adm_sched_threshold(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step,
+                        int lo, int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W, void* stream);
+/* adm_sched_step with x0 = clamp(x0, -s_b, s_b) / s_b in place of the `clip` clamp (the row's clip field is ignored): runs
+ * adm_sched_threshold into `scale` (B floats, device, caller-owned: it holds s_b afterwards) and then the step kernel on the same stream, so
+ * the selection has read x before an `out` that aliases x is written. With max_value == 1 every s_b is 1 and the result is bit-identical to
+ * adm_sched_step with clip = 1. */
+int adm_sched_step_thresholded(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
+                               const adm_sched_coef* coef_table, const int* step_dev, int step,
+                               const float* mask, int n_mask_steps, int mask_start, int mask_end,
+                               int B, int C, int H, int W, void* stream,
+                               int lo, int hi, float w, float max_value, float* scale);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -389,6 +411,12 @@ int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_h
 int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host,
                               int n_steps, const float* step_noise, const float* mask, int mask_start, int mask_end,
                               uint8_t* u8_out, int use_graph, void* stream);
+/* adm_sample_loop with the dynamically thresholded epilogue (adm_sched_step_thresholded; adm_version() >= 110): every step runs the
+ * selection and then the thresholded step kernel between the forward and the step counter's increment, inside the captured graph. lo, hi, w
+ * as in adm_sched_threshold for n = in_channels * sample_h * sample_w; the per-sample scale buffer belongs to the handle's plan. */
+int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
+                                const float* step_noise, const float* mask, int mask_start, int mask_end,
+                                uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
