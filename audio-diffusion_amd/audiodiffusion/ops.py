@@ -70,7 +70,7 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
 
 def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
                     u8_out=None, step_dev=None):
-    """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_multistep_kernel`). x, eps, hist: (B,C,H,W); k_hist_table: (n,) fp32
+    """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,) fp32
     beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev: optional
     int32 device scalar that replaces `step`."""
     _f32(x), _f32(eps), _f32(hist), _f32(k_hist_table)

@@ -284,7 +284,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     spacings, `final_sigmas_type` zero / sigma_min, `lower_order_final`, `euler_at_final`. Everything else raises
     NotImplementedError naming the key (the SDE variants need per-step noise and a history that survives the pipeline's
     noise-staging chunks). `thresholding=True` raises as well: the selection kernel of the DDIM / DDPM schedulers
-    (`adm_sched_threshold`) is what a thresholded multistep kernel would reuse, but that sibling kernel is not built."""
+    (`adm_sched_threshold`) is what a thresholded multistep step would reuse: one more instantiation of `sched_step_kernel`, which is not built."""
     _class_name = "DPMSolverMultistepScheduler"
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
                      solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,

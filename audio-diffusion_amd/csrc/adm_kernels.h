@@ -6,24 +6,19 @@
 namespace adm {
 
 // k_sched.hip
-int launch_sched_step(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8,
-                      const adm_sched_coef* table, const int* step_dev, int step, const float* mask,
-                      int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, hipStream_t st);
-int launch_sched_step_loop(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
-                           uint8_t* u8, int u8_step, const adm_sched_coef* table, const int* step_dev, int step,
-                           const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
-                           int W, hipStream_t st);
+enum { SCHED_PLAIN = 0, SCHED_THRESH = 1, SCHED_MULTISTEP = 2 };   // which sched_step_kernel<MODE> runs
+struct SchedStepParams {   // the step kernel's parameter block; the caller fills the first three lines and its mode's extras
+  const float* x; const float* eps; const float* noise; float* out; uint8_t* u8; const adm_sched_coef* table;
+  const int* step_dev; int step; const float* mask; int n_mask_steps, mask_start, mask_end, B, C, H, W;
+  long noise_step_stride = 0; int u8_step = -1;           // captured loop: per-step noise slice; the one step that writes u8 (-1: every)
+  int lo = 0, hi = 0; float w = 0.f, max_value = 1.f; float* scale = nullptr;   // SCHED_THRESH: ranks, weight, maximum; (B,) thresholds
+  float* hist = nullptr; const float* k_hist_table = nullptr;                   // SCHED_MULTISTEP
+  long per_sample = 0, n4 = 0, mask_bstride = 0;          // derived from the shape by launch_sched_step
+};
+int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st);
 int launch_step_advance(int* step_dev, hipStream_t st);
 int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
                            int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st);
-int launch_sched_step_thresholded(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
-                                  uint8_t* u8, int u8_step, const adm_sched_coef* table, const int* step_dev, int step,
-                                  const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
-                                  int W, int lo, int hi, float w, float max_value, float* scale, hipStream_t st);
-int launch_sched_multistep(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
-                           float* hist, uint8_t* u8, int u8_step, const adm_sched_coef* table, const float* k_hist_table,
-                           const int* step_dev, int step, const float* mask, int n_mask_steps, int mask_start,
-                           int mask_end, int B, int C, int H, int W, hipStream_t st);
 int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

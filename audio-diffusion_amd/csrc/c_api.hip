@@ -104,8 +104,8 @@ int adm_sched_step(const float* x, const float* eps, const float* noise, float* 
                    const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask,
                    int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, void* stream) {
   ADM_REQUIRE(x && eps && out && coef_table, "sched_step: null argument");
-  return launch_sched_step(x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start,
-                           mask_end, B, C, H, W, (hipStream_t)stream);
+  const SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream);
 }
 
 int adm_sched_multistep(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
@@ -113,8 +113,9 @@ int adm_sched_multistep(const float* x, const float* eps, const float* noise, fl
                         int step, const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
                         int W, void* stream) {
   ADM_REQUIRE(x && eps && out && coef_table && k_hist_table && hist, "sched_multistep: null argument");
-  return launch_sched_multistep(x, eps, noise, 0, out, hist, u8_out, -1, coef_table, k_hist_table, step_dev, step, mask,
-                                n_mask_steps, mask_start, mask_end, B, C, H, W, (hipStream_t)stream);
+  SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  p.hist = hist; p.k_hist_table = k_hist_table;
+  return launch_sched_step(p, SCHED_MULTISTEP, (hipStream_t)stream);
 }
 
 int adm_sched_threshold(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step, int lo,
@@ -129,8 +130,9 @@ int adm_sched_step_thresholded(const float* x, const float* eps, const float* no
                                int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, void* stream, int lo,
                                int hi, float w, float max_value, float* scale) {
   ADM_REQUIRE(x && eps && out && coef_table && scale, "sched_step_thresholded: null argument");
-  return launch_sched_step_thresholded(x, eps, noise, 0, out, u8_out, -1, coef_table, step_dev, step, mask, n_mask_steps,
-                                       mask_start, mask_end, B, C, H, W, lo, hi, w, max_value, scale, (hipStream_t)stream);
+  SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
+  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream);
 }
 
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

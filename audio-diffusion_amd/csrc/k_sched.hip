@@ -2,13 +2,17 @@
 // Replaces DDIMScheduler.step / DDPMScheduler.step + mask overwrite + final dequant
 // (reference: audiodiffusion/pipeline_audio_diffusion.py:165-185,192-194; SURVEY.md §8(a) S2-S4,P4,P5).
 // One float4 per lane per iteration, grid-stride; algorithmic bytes: 12 B/elem (x, eps in; out) +4 with noise.
-// sched_multistep_kernel is the same epilogue for the second-order multistep solver (DPM-Solver++ 2M): the update is linear in
-// (x, x0 of this step, x0 of the previous step), so it adds one per-step coefficient k_hist and one per-element history buffer that the
-// same lane reads and rewrites in place: +8 B/elem over sched_step_kernel (one history read, one history write), 20 B/elem in all.
-// sched_threshold_kernel + sched_step_thresh_kernel: dynamic thresholding (Imagen §2.3) of x0 in place of the static clamp. The per-sample
-// percentile of |x0| is an exact order statistic: one workgroup per sample, MSB-first radix select (11 + 10 + 10 bits) over an LDS histogram
-// of the bit pattern of |x0|; x0 is recomputed from x and eps in every pass (8 B/elem per pass, 3 passes + 1 when the two ranks straddle two
-// distinct values: 24-32 B/elem, L2-resident), nothing but the B scales goes to global memory.
+// sched_step_kernel<MODE> is ONE kernel for the three steps; the loop, the noise slice, the mask overwrite and the u8 pack are shared and only
+// the handful of lines that compute x0 and the update depend on MODE:
+//   SCHED_PLAIN      DDIM / DDPM with the row's static clamp.
+//   SCHED_MULTISTEP  the second-order multistep solver (DPM-Solver++ 2M): the update is linear in (x, x0 of this step, x0 of the previous
+//                    step), so it adds one per-step coefficient k_hist and one per-element history buffer that the same lane reads and
+//                    rewrites in place: +8 B/elem over SCHED_PLAIN (one history read, one history write), 20 B/elem in all.
+//   SCHED_THRESH     sched_threshold_kernel first: dynamic thresholding (Imagen §2.3) of x0 in place of the static clamp. The per-sample
+//                    percentile of |x0| is an exact order statistic: one workgroup per sample, MSB-first radix select (11 + 10 + 10 bits)
+//                    over an LDS histogram of the bit pattern of |x0|; x0 is recomputed from x and eps in every pass (8 B/elem per pass,
+//                    3 passes + 1 when the two ranks straddle two distinct values: 24-32 B/elem, L2-resident), nothing but the B scales
+//                    goes to global memory.
 #include "adm_kernels.h"
 
 namespace adm {
@@ -18,107 +22,75 @@ __device__ __forceinline__ float sched_x0(float x, float e, const adm_sched_coef
   return (x - c.sqrt_beta * e) / c.sqrt_alpha;
 }
 
-__device__ __forceinline__ float sched_one(float x, float e, float nz, const adm_sched_coef& c) {
-  float x0 = sched_x0(x, e, c);
-  if (c.clip >= 0.f) x0 = fminf(fmaxf(x0, -c.clip), c.clip);
-  float prev = c.k_x0 * x0 + c.k_x * x;
-  prev = prev + c.k_eps * e;
-  prev = prev + c.k_noise * nz;
-  return prev;
-}
-
-// x0 = clamp(x0, -s, s) / s with the sample's dynamic threshold s instead of the static clamp (c.clip is ignored)
-__device__ __forceinline__ float sched_one_thresh(float x, float e, float nz, const adm_sched_coef& c, float s) {
-  float x0 = sched_x0(x, e, c);
-  x0 = fminf(fmaxf(x0, -s), s) / s;
-  float prev = c.k_x0 * x0 + c.k_x * x;
-  prev = prev + c.k_eps * e;
-  prev = prev + c.k_noise * nz;
-  return prev;
-}
-
 __device__ __forceinline__ unsigned char quant_u8(float v) {
   float q = fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f) * 255.f;
   return (unsigned char)rintf(q);  // round-half-even == numpy .round() (pipeline:194)
 }
 
-__global__ void __launch_bounds__(256) sched_step_kernel(
-    const float* __restrict__ x, const float* __restrict__ eps, const float* noise, float* out,
-    unsigned char* u8, const adm_sched_coef* __restrict__ table, const int* __restrict__ step_dev,
-    int step, const float* __restrict__ mask, long mask_bstride, int mask_start, int mask_end, int W,
-    long per_sample, long n4, long noise_step_stride, int u8_step) {
-  const int s = step_dev ? *step_dev : step;
-  const adm_sched_coef c = table[s];
-  const bool use_noise = noise != nullptr && c.k_noise != 0.f;
-  noise += (long)s * noise_step_stride;  // per-step slice of a (n_steps,B,C,H,W) noise tensor (0: single step)
-  if (u8_step >= 0 && s != u8_step) u8 = nullptr;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 ev = reinterpret_cast<const float4*>(eps)[i];
-    float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
-    float r[4] = {sched_one(xv.x, ev.x, nv.x, c), sched_one(xv.y, ev.y, nv.y, c), sched_one(xv.z, ev.z, nv.z, c),
-                  sched_one(xv.w, ev.w, nv.w, c)};
-    if (mask != nullptr) {
-      const long e0 = i * 4;
-      const long b = e0 / per_sample;
-      const long p = e0 - b * per_sample;  // C == 1: p = row*W + col
-      const int col0 = (int)(p % W);
-      const float* mrow = mask + b * mask_bstride + (long)s * per_sample + p;
-      ADM_UNROLL
-      for (int k = 0; k < 4; ++k) {
-        const int col = col0 + k;
-        if (col < mask_start || col >= W - mask_end) r[k] = mrow[k];
-      }
-    }
-    reinterpret_cast<float4*>(out)[i] = make_float4(r[0], r[1], r[2], r[3]);
-    if (u8 != nullptr) {
-      const unsigned q = (unsigned)quant_u8(r[0]) | ((unsigned)quant_u8(r[1]) << 8) |
-                         ((unsigned)quant_u8(r[2]) << 16) | ((unsigned)quant_u8(r[3]) << 24);
-      reinterpret_cast<unsigned*>(u8)[i] = q;
-    }
-  }
+__device__ __forceinline__ unsigned pack_u8x4(float a, float b, float c, float d) {
+  return (unsigned)quant_u8(a) | ((unsigned)quant_u8(b) << 8) | ((unsigned)quant_u8(c) << 16) | ((unsigned)quant_u8(d) << 24);
 }
 
-// The same step with the dynamic threshold scale[b] of sample b (sched_threshold_kernel below) in place of the row's static clamp.
-__global__ void __launch_bounds__(256) sched_step_thresh_kernel(
-    const float* __restrict__ x, const float* __restrict__ eps, const float* noise, float* out,
-    unsigned char* u8, const adm_sched_coef* __restrict__ table, const int* __restrict__ step_dev,
-    int step, const float* __restrict__ mask, long mask_bstride, int mask_start, int mask_end, int W,
-    long per_sample, long n4, long noise_step_stride, int u8_step, const float* __restrict__ scale) {
-  const int s = step_dev ? *step_dev : step;
-  const adm_sched_coef c = table[s];
-  const bool use_noise = noise != nullptr && c.k_noise != 0.f;
-  noise += (long)s * noise_step_stride;  // per-step slice of a (n_steps,B,C,H,W) noise tensor (0: single step)
-  if (u8_step >= 0 && s != u8_step) u8 = nullptr;
+// x0 of this step, then prev: the three modes differ in these lines only, and on purpose (an unconditional `+ k * 0` turns -0.0 into +0.0):
+//   SCHED_PLAIN      x0 clamped to the row's c.clip (when >= 0);   prev = k_x0*x0 + k_x*x, += k_eps*eps, += k_noise*noise (noise 0 if unused)
+//   SCHED_THRESH     x0 = clamp(x0, -s, s) / s with the sample's dynamic threshold s = scale[b] (c.clip is ignored); prev as SCHED_PLAIN
+//   SCHED_MULTISTEP  m0 = x0 clamped as SCHED_PLAIN, m1 = x0 of the previous step from `hist`;
+//                    prev = k_x0*m0 + k_x*x, += k_hist*m1 only where k_hist != 0, += k_noise*noise only where noise is used;
+//                    hist = m0 (always, and before the mask: the history is the model's x0).
+//                    hist is read ONLY where k_hist != 0: the first row of a run has k_hist == 0 and finds the buffer uninitialised
+//                    (0 * NaN must not reach the output). Each lane reads and rewrites its own elements of hist.
+// out may alias x.
+template <int MODE>
+__global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p) {
+  const int s = p.step_dev ? *p.step_dev : p.step;
+  const adm_sched_coef c = p.table[s];
+  const float k_hist = MODE == SCHED_MULTISTEP ? p.k_hist_table[s] : 0.f;
+  const bool use_hist = k_hist != 0.f;
+  const bool use_noise = p.noise != nullptr && c.k_noise != 0.f;
+  const float* noise = p.noise + (long)s * p.noise_step_stride;  // per-step slice of a (n_steps,B,C,H,W) noise tensor (0: single step)
+  unsigned char* u8 = p.u8_step >= 0 && s != p.u8_step ? nullptr : p.u8;
   const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 ev = reinterpret_cast<const float4*>(eps)[i];
-    float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n4; i += stride) {
+    const float4 xv = reinterpret_cast<const float4*>(p.x)[i];
+    const float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
+    float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
-    const float th = scale[(i * 4) / per_sample];  // W % 4 == 0: a float4 never straddles two samples
-    float r[4] = {sched_one_thresh(xv.x, ev.x, nv.x, c, th), sched_one_thresh(xv.y, ev.y, nv.y, c, th),
-                  sched_one_thresh(xv.z, ev.z, nv.z, c, th), sched_one_thresh(xv.w, ev.w, nv.w, c, th)};
-    if (mask != nullptr) {
+    if (use_hist) hv = reinterpret_cast<const float4*>(p.hist)[i];
+    float th = 0.f;
+    if (MODE == SCHED_THRESH) th = p.scale[(i * 4) / p.per_sample];  // W % 4 == 0: a float4 never straddles two samples
+    float4 mv;  // x0 of this step, clamped: the next step's history
+    auto one = [&](float x, float e, float nz, float h, float& m0) {
+      float x0 = sched_x0(x, e, c);
+      if (MODE == SCHED_THRESH) x0 = fminf(fmaxf(x0, -th), th) / th;
+      else if (c.clip >= 0.f) x0 = fminf(fmaxf(x0, -c.clip), c.clip);
+      float prev = c.k_x0 * x0 + c.k_x * x;
+      if (MODE == SCHED_MULTISTEP) {
+        if (use_hist) prev = prev + k_hist * h;
+        if (use_noise) prev = prev + c.k_noise * nz;
+      } else {
+        prev = prev + c.k_eps * e;
+        prev = prev + c.k_noise * nz;
+      }
+      m0 = x0;
+      return prev;
+    };
+    float r[4] = {one(xv.x, ev.x, nv.x, hv.x, mv.x), one(xv.y, ev.y, nv.y, hv.y, mv.y), one(xv.z, ev.z, nv.z, hv.z, mv.z),
+                  one(xv.w, ev.w, nv.w, hv.w, mv.w)};
+    if (MODE == SCHED_MULTISTEP) reinterpret_cast<float4*>(p.hist)[i] = mv;
+    if (p.mask != nullptr) {
       const long e0 = i * 4;
-      const long b = e0 / per_sample;
-      const long p = e0 - b * per_sample;  // C == 1: p = row*W + col
-      const int col0 = (int)(p % W);
-      const float* mrow = mask + b * mask_bstride + (long)s * per_sample + p;
+      const long b = e0 / p.per_sample;
+      const long q = e0 - b * p.per_sample;  // C == 1: q = row*W + col
+      const int col0 = (int)(q % p.W);
+      const float* mrow = p.mask + b * p.mask_bstride + (long)s * p.per_sample + q;
       ADM_UNROLL
       for (int k = 0; k < 4; ++k) {
         const int col = col0 + k;
-        if (col < mask_start || col >= W - mask_end) r[k] = mrow[k];
+        if (col < p.mask_start || col >= p.W - p.mask_end) r[k] = mrow[k];
       }
     }
-    reinterpret_cast<float4*>(out)[i] = make_float4(r[0], r[1], r[2], r[3]);
-    if (u8 != nullptr) {
-      const unsigned q = (unsigned)quant_u8(r[0]) | ((unsigned)quant_u8(r[1]) << 8) |
-                         ((unsigned)quant_u8(r[2]) << 16) | ((unsigned)quant_u8(r[3]) << 24);
-      reinterpret_cast<unsigned*>(u8)[i] = q;
-    }
+    reinterpret_cast<float4*>(p.out)[i] = make_float4(r[0], r[1], r[2], r[3]);
+    if (u8 != nullptr) reinterpret_cast<unsigned*>(u8)[i] = pack_u8x4(r[0], r[1], r[2], r[3]);
   }
 }
 
@@ -240,64 +212,6 @@ __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
   }
 }
 
-// Multistep data-prediction update: m0 = x0 of this step (clipped as in sched_one), m1 = x0 of the previous step from `hist`;
-//   prev = k_x0*m0 + k_x*x + k_hist*m1 (+ k_noise*noise);  hist = m0 (always, and before the mask: the history is the model's x0).
-// hist is read ONLY where k_hist != 0: the first row of a run has k_hist == 0 and finds the buffer uninitialised (0 * NaN must not
-// reach the output). out may alias x; each lane reads and rewrites its own elements of hist.
-__global__ void __launch_bounds__(256) sched_multistep_kernel(
-    const float* x, const float* __restrict__ eps, const float* noise, float* out, float* hist, unsigned char* u8,
-    const adm_sched_coef* __restrict__ table, const float* __restrict__ k_hist_table, const int* __restrict__ step_dev,
-    int step, const float* __restrict__ mask, long mask_bstride, int mask_start, int mask_end, int W, long per_sample,
-    long n4, long noise_step_stride, int u8_step) {
-  const int s = step_dev ? *step_dev : step;
-  const adm_sched_coef c = table[s];
-  const float k_hist = k_hist_table[s];
-  const bool use_hist = k_hist != 0.f;
-  const bool use_noise = noise != nullptr && c.k_noise != 0.f;
-  noise += (long)s * noise_step_stride;
-  if (u8_step >= 0 && s != u8_step) u8 = nullptr;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 ev = reinterpret_cast<const float4*>(eps)[i];
-    float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
-    if (use_hist) hv = reinterpret_cast<const float4*>(hist)[i];
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, ns[4] = {nv.x, nv.y, nv.z, nv.w},
-                hs[4] = {hv.x, hv.y, hv.z, hv.w};
-    float r[4], m[4];
-    ADM_UNROLL
-    for (int k = 0; k < 4; ++k) {
-      float m0 = (xs[k] - c.sqrt_beta * es[k]) / c.sqrt_alpha;
-      if (c.clip >= 0.f) m0 = fminf(fmaxf(m0, -c.clip), c.clip);
-      float prev = c.k_x0 * m0 + c.k_x * xs[k];
-      if (use_hist) prev = prev + k_hist * hs[k];
-      if (use_noise) prev = prev + c.k_noise * ns[k];
-      m[k] = m0;
-      r[k] = prev;
-    }
-    reinterpret_cast<float4*>(hist)[i] = make_float4(m[0], m[1], m[2], m[3]);
-    if (mask != nullptr) {
-      const long e0 = i * 4;
-      const long b = e0 / per_sample;
-      const long p = e0 - b * per_sample;  // C == 1: p = row*W + col
-      const int col0 = (int)(p % W);
-      const float* mrow = mask + b * mask_bstride + (long)s * per_sample + p;
-      ADM_UNROLL
-      for (int k = 0; k < 4; ++k) {
-        const int col = col0 + k;
-        if (col < mask_start || col >= W - mask_end) r[k] = mrow[k];
-      }
-    }
-    reinterpret_cast<float4*>(out)[i] = make_float4(r[0], r[1], r[2], r[3]);
-    if (u8 != nullptr) {
-      const unsigned q = (unsigned)quant_u8(r[0]) | ((unsigned)quant_u8(r[1]) << 8) |
-                         ((unsigned)quant_u8(r[2]) << 16) | ((unsigned)quant_u8(r[3]) << 24);
-      reinterpret_cast<unsigned*>(u8)[i] = q;
-    }
-  }
-}
-
 __global__ void step_advance_kernel(int* step_dev) { *step_dev += 1; }
 
 // DDIM inversion update (pipeline_audio_diffusion.py:238-240).
@@ -339,34 +253,13 @@ __global__ void __launch_bounds__(256) dequant_kernel(const float* __restrict__ 
                                                       long n4) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
-    reinterpret_cast<unsigned*>(out)[i] = (unsigned)quant_u8(v.x) | ((unsigned)quant_u8(v.y) << 8) |
-                                          ((unsigned)quant_u8(v.z) << 16) | ((unsigned)quant_u8(v.w) << 24);
+    reinterpret_cast<unsigned*>(out)[i] = pack_u8x4(v.x, v.y, v.z, v.w);
   }
 }
 
 static inline int ew_grid(long n4) {
   long g = (n4 + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));  // cap + grid-stride (guide §6 G11)
-}
-
-int launch_sched_step_loop(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
-                           uint8_t* u8, int u8_step, const adm_sched_coef* table, const int* step_dev, int step,
-                           const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
-                           int W, hipStream_t st) {
-  const long per_sample = (long)C * H * W, n = per_sample * B;
-  ADM_REQUIRE(W % 4 == 0, "sched_step: W must be a multiple of 4");
-  ADM_REQUIRE(mask == nullptr || C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
-  ADM_LAUNCH(sched_step_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, eps, noise, out, u8, table, step_dev, step,
-             mask, (long)n_mask_steps * per_sample, mask_start, mask_end, W, per_sample, n / 4, noise_step_stride,
-             u8_step);
-  return ADM_CHECK_LAUNCH();
-}
-
-int launch_sched_step(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8,
-                      const adm_sched_coef* table, const int* step_dev, int step, const float* mask,
-                      int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, hipStream_t st) {
-  return launch_sched_step_loop(x, eps, noise, 0, out, u8, -1, table, step_dev, step, mask, n_mask_steps, mask_start,
-                                mask_end, B, C, H, W, st);
 }
 
 int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
@@ -382,30 +275,28 @@ int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coe
   return ADM_CHECK_LAUNCH();
 }
 
-// selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written
-int launch_sched_step_thresholded(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
-                                  uint8_t* u8, int u8_step, const adm_sched_coef* table, const int* step_dev, int step,
-                                  const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
-                                  int W, int lo, int hi, float w, float max_value, float* scale, hipStream_t st) {
-  const long per_sample = (long)C * H * W, n = per_sample * B;
-  ADM_REQUIRE(mask == nullptr || C == 1, "sched_step_thresholded: mask path requires C == 1 (as in the reference)");
-  ADM_TRY(launch_sched_threshold(x, eps, table, step_dev, step, lo, hi, w, max_value, scale, B, C, H, W, st));
-  ADM_LAUNCH(sched_step_thresh_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, eps, noise, out, u8, table, step_dev, step,
-             mask, (long)n_mask_steps * per_sample, mask_start, mask_end, W, per_sample, n / 4, noise_step_stride, u8_step,
-             (const float*)scale);
-  return ADM_CHECK_LAUNCH();
-}
-
-int launch_sched_multistep(const float* x, const float* eps, const float* noise, long noise_step_stride, float* out,
-                           float* hist, uint8_t* u8, int u8_step, const adm_sched_coef* table, const float* k_hist_table,
-                           const int* step_dev, int step, const float* mask, int n_mask_steps, int mask_start,
-                           int mask_end, int B, int C, int H, int W, hipStream_t st) {
-  const long per_sample = (long)C * H * W, n = per_sample * B;
-  ADM_REQUIRE(W % 4 == 0, "sched_multistep: W must be a multiple of 4");
-  ADM_REQUIRE(mask == nullptr || C == 1, "sched_multistep: mask path requires C == 1 (as in the reference)");
-  ADM_LAUNCH(sched_multistep_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, eps, noise, out, hist, u8, table,
-             k_hist_table, step_dev, step, mask, (long)n_mask_steps * per_sample, mask_start, mask_end, W, per_sample, n / 4,
-             noise_step_stride, u8_step);
+// SCHED_THRESH: selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written
+int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st) {
+  SchedStepParams p = in;
+  p.per_sample = (long)p.C * p.H * p.W;
+  p.n4 = p.per_sample * p.B / 4;
+  p.mask_bstride = (long)p.n_mask_steps * p.per_sample;
+  const dim3 grid(ew_grid(p.n4)), block(256);
+  if (mode == SCHED_THRESH) {
+    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_thresholded: mask path requires C == 1 (as in the reference)");
+    ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,
+                                   p.W, st));
+    ADM_LAUNCH(sched_step_kernel<SCHED_THRESH>, grid, block, 0, st, p);
+  } else if (mode == SCHED_MULTISTEP) {
+    ADM_REQUIRE(p.W % 4 == 0, "sched_multistep: W must be a multiple of 4");
+    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_multistep: mask path requires C == 1 (as in the reference)");
+    ADM_LAUNCH(sched_step_kernel<SCHED_MULTISTEP>, grid, block, 0, st, p);
+  } else {
+    ADM_REQUIRE(mode == SCHED_PLAIN, "sched_step: unknown mode");
+    ADM_REQUIRE(p.W % 4 == 0, "sched_step: W must be a multiple of 4");
+    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
+    ADM_LAUNCH(sched_step_kernel<SCHED_PLAIN>, grid, block, 0, st, p);
+  }
   return ADM_CHECK_LAUNCH();
 }
 

@@ -336,12 +336,12 @@ static int ensure_khist(adm_unet* h, const float* k_hist_host, int n, hipStream_
   return copy_h2d(h->khist_dev, k_hist_host, sizeof(float) * (size_t)n, st);
 }
 
-enum { LOOP_SAMPLE = 0, LOOP_ENCODE = 1, LOOP_MULTISTEP = 2, LOOP_THRESH = 3 };   // which step kernel follows the forward
+enum { LOOP_ENCODE = -1 };   // LoopArgs::mode: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
 
 struct LoopArgs {
   float* x; int B; int n_steps; const float* step_noise; const float* mask; int mask_start, mask_end;
   uint8_t* u8; int mode; const float* k_hist_host;
-  int th_lo = 0, th_hi = 0; float th_w = 0.f, th_max = 1.f;   // LOOP_THRESH: the two ranks, their weight and sample_max_value
+  int th_lo = 0, th_hi = 0; float th_w = 0.f, th_max = 1.f;   // SCHED_THRESH: the two ranks, their weight and sample_max_value
 };
 
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
@@ -352,18 +352,13 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
   const long n = (long)a.B * c.in_channels * c.sample_h * c.sample_w;
   if (a.mode == LOOP_ENCODE) {
     ADM_TRY(launch_encode_step(a.x, h->eps_buf, table, h->step_dev, step, n, st));
-  } else if (a.mode == LOOP_MULTISTEP) {
-    ADM_TRY(launch_sched_multistep(a.x, h->eps_buf, a.step_noise, n, a.x, h->hist_buf, a.u8, a.n_steps - 1, table,
-                                   h->khist_dev, h->step_dev, step, a.mask, a.n_steps, a.mask_start, a.mask_end, a.B,
-                                   c.in_channels, c.sample_h, c.sample_w, st));
-  } else if (a.mode == LOOP_THRESH) {
-    ADM_TRY(launch_sched_step_thresholded(a.x, h->eps_buf, a.step_noise, n, a.x, a.u8, a.n_steps - 1, table, h->step_dev, step,
-                                          a.mask, a.n_steps, a.mask_start, a.mask_end, a.B, c.in_channels, c.sample_h,
-                                          c.sample_w, a.th_lo, a.th_hi, a.th_w, a.th_max, h->scale_buf, st));
   } else {
-    ADM_TRY(launch_sched_step_loop(a.x, h->eps_buf, a.step_noise, n, a.x, a.u8, a.n_steps - 1, table, h->step_dev, step,
-                                   a.mask, a.n_steps, a.mask_start, a.mask_end, a.B, c.in_channels, c.sample_h,
-                                   c.sample_w, st));
+    SchedStepParams p{a.x, h->eps_buf, a.step_noise, a.x, a.u8, table, h->step_dev, step, a.mask, a.n_steps, a.mask_start,
+                      a.mask_end, a.B, c.in_channels, c.sample_h, c.sample_w};
+    p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
+    p.lo = a.th_lo; p.hi = a.th_hi; p.w = a.th_w; p.max_value = a.th_max; p.scale = h->scale_buf;
+    p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
+    ADM_TRY(launch_sched_step(p, a.mode, st));
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
   return 0;
@@ -376,7 +371,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
 #if defined(ADM_EMU)
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
-  if (a.mode == LOOP_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
+  if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
   for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
   return 0;
 #else
@@ -390,7 +385,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
     ADM_HIP_OK(hipStreamWaitEvent(run, ev, 0));
   }
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, run));
-  if (a.mode == LOOP_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
+  if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
   if (!use_graph) {
     for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
   } else {
@@ -398,8 +393,8 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
                                  (uint64_t)a.mask, (uint64_t)a.mask_start, (uint64_t)a.mask_end, (uint64_t)a.u8,
                                  (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
                                  (uint64_t)h->net.ctx_S};
-    if (a.mode == LOOP_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
-    if (a.mode == LOOP_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
+    if (a.mode == SCHED_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
+    if (a.mode == SCHED_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
       uint32_t wb, mb;
       memcpy(&wb, &a.th_w, 4); memcpy(&mb, &a.th_max, 4);
       key.push_back((uint64_t)h->scale_buf); key.push_back((uint64_t)a.th_lo); key.push_back((uint64_t)a.th_hi);
@@ -443,6 +438,15 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
   }
   return 0;
 #endif
+}
+
+// What every loop entry point does after its own argument checks.
+static int run_loop_fp32(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_host, int use_graph, void* stream) {
+  Bf16Scope fp32(0);
+  ADM_TRY(finalize(h));
+  InferenceScope inf(&h->net, (hipStream_t)stream);
+  ADM_TRY(inf.rc);
+  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
 }
 
 }  // namespace adm
@@ -673,12 +677,8 @@ int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_h
                     const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out,
                     int use_graph, void* stream) {
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop: bad argument");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_SAMPLE, nullptr};
-  Bf16Scope fp32(0);
-  ADM_TRY(finalize(h));
-  InferenceScope inf(&h->net, (hipStream_t)stream);
-  ADM_TRY(inf.rc);
-  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_PLAIN, nullptr};
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 
 int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host,
@@ -686,36 +686,24 @@ int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_co
                               uint8_t* u8_out, int use_graph, void* stream) {
   ADM_REQUIRE(h && x && coef_host && k_hist_host && n_steps > 0, "sample_loop_multistep: bad argument");
   ADM_REQUIRE(k_hist_host[0] == 0.f, "sample_loop_multistep: the first row of a run must be first order (k_hist[0] == 0)");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_MULTISTEP, k_hist_host};
-  Bf16Scope fp32(0);
-  ADM_TRY(finalize(h));
-  InferenceScope inf(&h->net, (hipStream_t)stream);
-  ADM_TRY(inf.rc);
-  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_MULTISTEP, k_hist_host};
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 
 int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                                 const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out,
                                 int use_graph, void* stream, int lo, int hi, float w, float max_value) {
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop_thresholded: bad argument");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, LOOP_THRESH, nullptr};
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_THRESH, nullptr};
   a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value;
-  Bf16Scope fp32(0);
-  ADM_TRY(finalize(h));
-  InferenceScope inf(&h->net, (hipStream_t)stream);
-  ADM_TRY(inf.rc);
-  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream) {
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "encode_loop: bad argument");
   LoopArgs a{x, B, n_steps, nullptr, nullptr, 0, 0, nullptr, LOOP_ENCODE, nullptr};
-  Bf16Scope fp32(0);
-  ADM_TRY(finalize(h));
-  InferenceScope inf(&h->net, (hipStream_t)stream);
-  ADM_TRY(inf.rc);
-  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 
 }  // extern "C"

@@ -217,6 +217,32 @@ def test_kernel_against_float64(backend, shape, v):
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
+def test_sign_of_zero_tells_the_three_update_tails_apart(backend):
+    """x = -0.0, eps = +0.0: x0 and k_x0*x0 + k_x*x are -0.0 (sums and products of zeros are exact, fused or not). The plain and the
+    thresholded step then add k_eps*eps = +0.0 unconditionally, which gives +0.0; the multistep step has no k_eps term and skips the
+    history (k_hist == 0) and the noise, so it keeps -0.0, in `out` and in `hist`, and never reads the NaN-filled history."""
+    from audiodiffusion import ops
+    dev = select(backend)
+    shape = (1, 1, 4, 8)
+    row = dict(sqrt_beta=_f32(0.6), sqrt_alpha=_f32(0.8), clip=-1.0, k_x0=_f32(0.9), k_x=_f32(0.3), k_eps=_f32(0.2), k_noise=0.0,
+               timestep=0.0)
+    table = ops.sched_coef_table([row], dev)
+    x, e = torch.full(shape, -0.0).to(dev), torch.zeros(shape).to(dev)
+    hist = torch.full(shape, float("nan")).to(dev)
+    kh = torch.zeros((1,), dtype=torch.float32).to(dev)
+
+    def bits(t):
+        return t.cpu().view(torch.int32).flatten().tolist()
+
+    n = x.numel()
+    assert bits(x) == [-0x80000000] * n
+    assert bits(ops.sched_step(x, e, table, 0)) == [0] * n
+    assert bits(ops.sched_step(x, e, table, 0, threshold=(0.995, 2.0))) == [0] * n
+    assert bits(ops.sched_multistep(x, e, table, kh, hist, 0)) == [-0x80000000] * n
+    assert bits(hist) == [-0x80000000] * n
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
 def test_kernel_bits_of_a_sample_do_not_depend_on_its_batch(backend):
     dev = select(backend)
     shape = (3, 2, 8, 12)

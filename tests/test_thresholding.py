@@ -600,7 +600,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_scheduler_kernels_compile_without_spills():
-    """The static check of tests/test_no_spill.py on k_sched.hip, which holds the selection and the thresholded step."""
+    """The static check of tests/test_no_spill.py on k_sched.hip, which holds the selection and the three instantiations of the step."""
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "audio-diffusion_amd", "csrc")
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "k_sched.hip", "-o", os.devnull,
                         "-Rpass-analysis=kernel-resource-usage"], cwd=csrc, capture_output=True, text=True, timeout=600)
@@ -613,5 +613,6 @@ def test_scheduler_kernels_compile_without_spills():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and name:
             usage[name] = int(m.group(1))
-    assert any("sched_threshold_kernel" in k for k in usage) and any("sched_step_thresh_kernel" in k for k in usage), usage
+    assert any("sched_threshold_kernel" in k for k in usage), usage
+    assert len({k for k in usage if "sched_step_kernel" in k}) == 3, usage   # the plain, thresholded and multistep instantiations
     assert all(v == 0 for v in usage.values()), usage
