@@ -31,28 +31,48 @@ def threshold_ranks(n, ratio):
     return int(lo), int(np.ceil(rank)), float(np.float32(rank - lo))
 
 
-def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None):
+PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}   # the C-ABI's `prediction`
+
+
+def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None, prediction=0):
     """Per-sample dynamic threshold s_b = clamp(quantile(|x0_b|, ratio), 1, max_value) of x0 = (x - sqrt_beta*eps) / sqrt_alpha
-    (csrc/k_sched.hip `sched_threshold_kernel`: an exact radix select on the device, equal to torch.quantile to the bit). -> (B,) fp32."""
+    (csrc/k_sched.hip `sched_threshold_kernel`: an exact radix select on the device, equal to torch.quantile to the bit). -> (B,) fp32.
+    prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model and x0 is formed accordingly
+    (`adm_sched_threshold_pred`)."""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
     lo, hi, w = threshold_ranks(Cc * H * W, ratio)
     out = torch.empty((B,), dtype=torch.float32, device=x.device) if out is None else out
+    if prediction != 0:
+        N.check(N.lib().adm_sched_threshold_pred(N.ptr(x), N.ptr(eps), N.ptr(coef_table), N.ptr(step_dev), int(step), lo, hi, w,
+                                                 float(max_value), N.ptr(out), B, Cc, H, W, N.stream_for(x), int(prediction)))
+        return out
     N.check(N.lib().adm_sched_threshold(N.ptr(x), N.ptr(eps), N.ptr(coef_table), N.ptr(step_dev), int(step), lo, hi, w,
                                         float(max_value), N.ptr(out), B, Cc, H, W, N.stream_for(x)))
     return out
 
 
 def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
-               step_dev=None, scale_out=None):
+               step_dev=None, scale_out=None, prediction=0):
     """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194). x,eps: (B,C,H,W). threshold: None, or
     (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it instead of the static
     clamp (`adm_sched_step_thresholded`; scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device
-    scalar that replaces `step`."""
+    scalar that replaces `step`. prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model
+    (`adm_sched_step_pred`; include/adm.h has the table)."""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
     out = torch.empty_like(x) if out is None else out
     n_mask = mask.shape[1] if mask is not None else 0
+    if prediction != 0:
+        lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
+        if threshold is not None:
+            lo, hi, w = threshold_ranks(Cc * H * W, threshold[0])
+            max_value = threshold[1]
+            scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+        N.check(N.lib().adm_sched_step_pred(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
+                                            N.ptr(step_dev), int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H,
+                                            W, N.stream_for(x), lo, hi, w, float(max_value), N.ptr(scale), int(prediction)))
+        return out
     if threshold is not None:
         ratio, max_value = threshold
         lo, hi, w = threshold_ranks(Cc * H * W, ratio)
@@ -100,6 +120,17 @@ def add_noise(x0, noise, sa, sb, per_sample):
         N.check(N.lib().adm_add_noise(N.ptr(x0), 0, N.ptr(noise), N.ptr(sa), N.ptr(sb), 0, 1, N.ptr(out), B, n, P,
                                       N.stream_for(noise)))
     return out
+
+
+def noise_and_velocity(x0, noise, sa, sb):
+    """Training prologue of a v_prediction model, one kernel: x0, noise (B,...) with sa, sb (B,) ->
+    (noisy = sa*x0 + sb*noise, bit-identical to add_noise(per_sample=True); velocity = sa*noise - sb*x0)."""
+    _f32(x0), _f32(noise), _f32(sa), _f32(sb)
+    assert x0.shape == noise.shape and sa.numel() == noise.shape[0] == sb.numel()
+    noisy, velocity = torch.empty_like(noise), torch.empty_like(noise)
+    N.check(N.lib().adm_noise_and_velocity(N.ptr(x0), N.ptr(noise), N.ptr(sa), N.ptr(sb), N.ptr(noisy), N.ptr(velocity),
+                                           noise.shape[0], noise[0].numel(), N.stream_for(noise)))
+    return noisy, velocity
 
 
 def dequant_u8(x):

@@ -158,6 +158,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         sched, unet = self.scheduler, self.unet
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
         thresh = None if multistep else sched.threshold()
+        pred = 0 if multistep else sched.prediction   # 0 epsilon: today's three entry points; otherwise adm_sample_loop_pred
         # (a multistep run that starts late starts first order: its rows depend on where it starts, not only on the slice)
         rows = sched.loop_rows(start_step, stop_step) if multistep else sched.coef_rows(eta)[start_step:stop_step]
         n = len(rows)
@@ -204,6 +205,11 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
                 N.check(N.lib().adm_sample_loop_multistep(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
                                                           int(mask_end), u8_ptr, int(use_graph), N.stream_for(x)))
+            elif pred != 0:   # a sample / v_prediction model: the same loop with the step (and selection) kernel of that type
+                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
+                N.check(N.lib().adm_sample_loop_pred(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start), int(mask_end),
+                                                     u8_ptr, int(use_graph), N.stream_for(x), lo, hi, w,
+                                                     thresh[1] if thresh is not None else 1.0, int(thresh is not None), pred))
             elif thresh is not None:   # dynamic thresholding: the statistic is over this tensor's C*H*W (the latent's, with a VAE)
                 lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0])
                 N.check(N.lib().adm_sample_loop_thresholded(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start),
@@ -320,6 +326,9 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         """Reverse step process: recover noisy image from generated image (`pipeline_audio_diffusion.py:207-242`)."""
         # Only works with DDIM as this method is deterministic
         assert isinstance(self.scheduler, DDIMScheduler)
+        if self.scheduler.config.prediction_type != "epsilon":
+            raise NotImplementedError(f"encode() is not implemented for prediction_type={self.scheduler.config.prediction_type!r} "
+                                      f"(epsilon only)")
         if isinstance(self.unet, UNet2DConditionModel):   # the reference calls self.unet(sample, t) here (:237): no encoding
             raise NotImplementedError("encode() is defined for the unconditional UNet2DModel only, as in the reference")
         self.scheduler.set_timesteps(steps)

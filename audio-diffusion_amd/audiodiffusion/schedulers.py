@@ -10,6 +10,12 @@ not used by the reference itself) goes through the sibling kernel and loop (`adm
 `adm_sample_loop_multistep`): one more coefficient per step and a per-element history of the previous x0 prediction.
 `thresholding=True` (DDPM / DDIM) replaces the static clamp of x0 by the dynamic one: a per-sample percentile selected on the
 device (`adm_sched_threshold`) in front of the step kernel, in `step()` and inside the captured loop (`adm_sample_loop_thresholded`).
+`prediction_type` "sample" / "v_prediction" (DDPM / DDIM): the model output is the clean sample or the velocity sa*eps - sb*x0 instead
+of the noise. The coefficient rows do not change; the step and selection kernels turn (x, output) into (x0, eps) by the type
+(`adm_sched_step_pred`, `adm_sched_threshold_pred`, `adm_sample_loop_pred`; the table is in include/adm.h), and `get_velocity` /
+`ops.noise_and_velocity` give the training target. With them come `timestep_spacing` "linspace" / "trailing" and
+`rescale_betas_zero_snr` (Lin et al. 2023), whose last training timestep has alphas_cumprod == 0: only the two new types can start
+there, an epsilon scheduler refuses such a schedule. The multistep scheduler stays epsilon-only.
 """
 import json
 import math
@@ -50,13 +56,26 @@ def _betas(n, beta_start, beta_end, schedule):
     raise NotImplementedError(f"{schedule} is not implemented")
 
 
+def _rescale_zero_snr(betas):
+    """[3P-recall] diffusers' `rescale_zero_terminal_snr` (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are
+    Flawed", algorithm 1), in the same fp32 tensor arithmetic: shift sqrt(alphas_cumprod) so that its last entry is 0, rescale so that
+    its first entry is kept, square, and take ratios back to betas. The last beta is exactly 1 (alphas_cumprod[-1] == 0)."""
+    alphas_bar_sqrt = torch.cumprod(1.0 - betas, dim=0).sqrt()
+    first, last = alphas_bar_sqrt[0].clone(), alphas_bar_sqrt[-1].clone()
+    alphas_bar_sqrt = alphas_bar_sqrt - last
+    alphas_bar_sqrt = alphas_bar_sqrt * (first / (first - last))
+    alphas_bar = alphas_bar_sqrt ** 2
+    alphas = torch.cat([alphas_bar[0:1], alphas_bar[1:] / alphas_bar[:-1]])
+    return 1 - alphas
+
+
 class _SchedulerBase:
     config_name = "scheduler_config.json"
     _class_name = "SchedulerMixin"
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                      trained_betas=None, clip_sample=True, clip_sample_range=1.0, prediction_type="epsilon",
                      timestep_spacing="leading", steps_offset=0, thresholding=False,
-                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0)
+                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0, rescale_betas_zero_snr=False)
 
     def __init__(self, **kwargs):
         cfg = dict(self._defaults)
@@ -69,6 +88,8 @@ class _SchedulerBase:
             self.betas = torch.tensor(cfg["trained_betas"], dtype=torch.float32)
         else:
             self.betas = _betas(cfg["num_train_timesteps"], cfg["beta_start"], cfg["beta_end"], cfg["beta_schedule"])
+        if cfg.get("rescale_betas_zero_snr"):
+            self.betas = _rescale_zero_snr(self.betas)
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.one = torch.tensor(1.0)
@@ -78,10 +99,11 @@ class _SchedulerBase:
         self._table = None  # (device, eta) -> device coefficient table
 
     def _check_config(self, cfg):
-        if cfg["prediction_type"] != "epsilon":
-            raise NotImplementedError("only prediction_type='epsilon' (what the reference trains) is implemented")
-        if cfg["timestep_spacing"] != "leading":
-            raise NotImplementedError("only timestep_spacing='leading' is implemented")
+        if cfg["prediction_type"] not in ops.PREDICTION_TYPES:
+            raise ValueError(f"prediction_type={cfg['prediction_type']!r} must be one of {', '.join(map(repr, ops.PREDICTION_TYPES))}")
+        if cfg["timestep_spacing"] not in ("leading", "linspace", "trailing"):
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r} is not implemented (implemented: 'leading', "
+                                      f"'linspace', 'trailing')")
         # dynamic thresholding (Imagen §2.3; diffusers' `_threshold_sample` [3P-recall]): checked whether or not it is switched on
         if not 0.0 <= float(cfg["dynamic_thresholding_ratio"]) <= 1.0:
             raise ValueError(f"dynamic_thresholding_ratio={cfg['dynamic_thresholding_ratio']!r} must be in [0, 1]")
@@ -111,12 +133,46 @@ class _SchedulerBase:
         n_train = self.config.num_train_timesteps
         if num_inference_steps > n_train:
             raise ValueError("num_inference_steps cannot exceed num_train_timesteps")
+        spacing = self.config.timestep_spacing
+        if spacing == "linspace":      # [3P-recall] the two other spacings of diffusers' DDIM / DDPM schedulers
+            ts = np.linspace(0, n_train - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+        elif spacing == "trailing":    # starts at T - 1: the zero-SNR timestep of a rescaled schedule
+            ts = (np.round(np.arange(n_train, 0, -n_train / num_inference_steps)) - 1).astype(np.int64)
+        else:
+            step_ratio = n_train // num_inference_steps
+            ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].copy().astype(np.int64)
+            ts += self.config.steps_offset
+        if spacing != "leading" and (np.diff(ts) >= 0).any():
+            # (diffusers lets them repeat; here `_index_of` would resolve every repeat to its first row, so eager steps and the loop
+            #  would part ways)
+            raise ValueError(f"{num_inference_steps} steps with timestep_spacing={spacing!r} over {n_train} training timesteps give "
+                             f"repeated timesteps; use fewer steps")
+        self._refuse_epsilon_at_zero_snr(ts)
         self.num_inference_steps = num_inference_steps
-        step_ratio = n_train // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].copy().astype(np.int64)
-        ts += self.config.steps_offset
         self.timesteps = torch.from_numpy(ts)
         self._table = None
+
+    @property
+    def prediction(self):
+        """The C-ABI's integer for `prediction_type`: 0 epsilon, 1 sample, 2 v_prediction."""
+        return ops.PREDICTION_TYPES[self.config.prediction_type]
+
+    def _refuse_epsilon_at_zero_snr(self, timesteps):
+        """x0 = (x - sb*eps) / sa divides by sa = 0 on a zero-SNR row (`rescale_betas_zero_snr` with a spacing that reaches T - 1).
+        The mirror image for a sample model: eps = (x - sa*x0) / sb divides by sb = 0 on a row with alphas_cumprod == 1, which only
+        `trained_betas` with leading zeros can make."""
+        if self.config.prediction_type == "sample":
+            for t in np.asarray(timesteps).tolist():
+                if float(self.alphas_cumprod[t]) == 1.0:
+                    raise ValueError(f"prediction_type='sample' cannot step from timestep {t}, where alphas_cumprod == 1 (no noise): "
+                                     f"eps = (x - sqrt_alpha*x0) / sqrt_beta divides by zero; drop the zero betas or that timestep")
+        if self.config.prediction_type != "epsilon":
+            return
+        for t in np.asarray(timesteps).tolist():
+            if float(self.alphas_cumprod[t]) == 0.0:
+                raise ValueError(f"prediction_type='epsilon' cannot step from timestep {t}, where alphas_cumprod == 0 (zero terminal "
+                                 f"SNR): x0 = (x - sqrt_beta*eps) / sqrt_alpha divides by zero; use prediction_type='v_prediction' or "
+                                 f"'sample', or a timestep_spacing that does not reach it")
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -138,6 +194,23 @@ class _SchedulerBase:
             # pipeline:150: (1,H,W) x (B,1,H,W) with one timestep -> (B,1,H,W)
             return ops.add_noise(x0.reshape(1, *x0.shape[-2:]).contiguous(), nz, sa, sb, per_sample=False)
         raise NotImplementedError("add_noise: unsupported broadcast pattern for the fused kernel")
+
+    def _sa_sb(self, timesteps, device):
+        ac = self.alphas_cumprod
+        ts = torch.as_tensor(timesteps).cpu().long()
+        return (ac[ts] ** 0.5).flatten().to(device).contiguous(), ((1 - ac[ts]) ** 0.5).flatten().to(device).contiguous()
+
+    def add_noise_and_velocity(self, original_samples, noise, timesteps):
+        """(add_noise, get_velocity) of the per-sample 4-D case from ONE kernel: what a v_prediction training step needs."""
+        x0, nz = original_samples.contiguous(), noise.contiguous()
+        sa, sb = self._sa_sb(timesteps, nz.device)
+        if not (nz.dim() == 4 and x0.shape == nz.shape and sa.numel() == nz.shape[0]):
+            raise NotImplementedError("get_velocity: only (B,C,H,W) samples and noise with one timestep per sample run in the fused kernel")
+        return ops.noise_and_velocity(x0, nz, sa, sb)
+
+    def get_velocity(self, sample, noise, timesteps):
+        """sqrt(acp[t])*noise - sqrt(1-acp[t])*sample, the regression target of a v_prediction model (diffusers' name) [3P-recall]."""
+        return self.add_noise_and_velocity(sample, noise, timesteps)[1]
 
     def _index_of(self, timestep):
         t = int(timestep)
@@ -179,7 +252,7 @@ class _SchedulerBase:
             variance_noise = randn_tensor(model_output.shape, generator, model_output.device, model_output.dtype)
         prev = ops.sched_step(sample.contiguous(), model_output.contiguous(), table, i,
                               noise=variance_noise.contiguous() if variance_noise is not None else None,
-                              threshold=self.threshold())
+                              threshold=self.threshold(), prediction=self.prediction)
         return SchedulerOutput(prev_sample=prev)
 
 
@@ -196,6 +269,7 @@ class DDPMScheduler(_SchedulerBase):
         return self.one
 
     def coef_rows(self, eta=0.0):
+        self._refuse_epsilon_at_zero_snr(self.timesteps)
         rows = []
         for t in self.timesteps.tolist():
             a_t = self.alphas_cumprod[t]
@@ -229,6 +303,7 @@ class DDIMScheduler(_SchedulerBase):
         return self.final_alpha_cumprod
 
     def coef_rows(self, eta=0.0):
+        self._refuse_epsilon_at_zero_snr(self.timesteps)
         rows = []
         for t in self.timesteps.tolist():
             a_t = self.alphas_cumprod[t]
@@ -245,6 +320,9 @@ class DDIMScheduler(_SchedulerBase):
     def encode_rows(self):
         """Coefficients of the DDIM inversion update, `pipeline_audio_diffusion.py:228-240`, in loop order
         (ascending timesteps): x = (x - c_dir*eps) * a_prev^-0.5 * a_t^0.5 + b_t^0.5 * eps."""
+        if self.config.prediction_type != "epsilon":
+            # the reference's inversion uses the model output as eps at a mismatched noise level; not generalised to the other types
+            raise NotImplementedError(f"encode() is not implemented for prediction_type={self.config.prediction_type!r} (epsilon only)")
         rows = []
         for t in torch.flip(self.timesteps, (0,)).tolist():
             a_t = self.alphas_cumprod[t]
@@ -294,10 +372,15 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
 
     def __init__(self, **kwargs):
         # keys of another scheduler's config (`from_config(pipe.scheduler.config)`) are dropped, as diffusers does
+        if kwargs.get("rescale_betas_zero_snr"):   # not dropped with the other foreign keys: it changes the schedule
+            raise NotImplementedError("rescale_betas_zero_snr=True is not implemented for DPMSolverMultistepScheduler (epsilon only: "
+                                      "sigma is infinite at the zero-SNR timestep)")
         known = {k: v for k, v in kwargs.items() if k in self._defaults}
         super().__init__(**known)
         self._unknown = {k: v for k, v in kwargs.items() if k not in self._defaults and not k.startswith("_")}
         self._reset_multistep()
+
+    prediction = 0   # epsilon only (`_check_config`)
 
     def _check_config(self, cfg):
         def only(key, allowed):

@@ -7,6 +7,7 @@ namespace adm {
 
 // k_sched.hip
 enum { SCHED_PLAIN = 0, SCHED_THRESH = 1, SCHED_MULTISTEP = 2 };   // which sched_step_kernel<MODE> runs
+enum { PRED_EPSILON = 0, PRED_SAMPLE = 1, PRED_V = 2 };            // what the model output is (the C-ABI's `prediction`); not 0: sched_step_pred_kernel<MODE, PRED>
 struct SchedStepParams {   // the step kernel's parameter block; the caller fills the first three lines and its mode's extras
   const float* x; const float* eps; const float* noise; float* out; uint8_t* u8; const adm_sched_coef* table;
   const int* step_dev; int step; const float* mask; int n_mask_steps, mask_start, mask_end, B, C, H, W;
@@ -15,14 +16,17 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
   float* hist = nullptr; const float* k_hist_table = nullptr;                   // SCHED_MULTISTEP
   long per_sample = 0, n4 = 0, mask_bstride = 0;          // derived from the shape by launch_sched_step
 };
-int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st);
+int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
 int launch_step_advance(int* step_dev, hipStream_t st);
 int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
-                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st);
+                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st,
+                           int pred = PRED_EPSILON);
 int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,
                      int cn, float* out, int B, int N, long P, hipStream_t st);
+int launch_noise_and_velocity(const float* x0, const float* noise, const float* sa, const float* sb, float* noisy, float* velocity,
+                              int B, long P, hipStream_t st);
 int launch_slerp_grid(const float* x0, const float* x1, long n, const double* alphas_dev, int n_alpha, float* out,
                       double* scratch3, hipStream_t st);
 int launch_dequant(const float* x, uint8_t* out, long n, hipStream_t st);

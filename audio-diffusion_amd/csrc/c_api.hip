@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 110; }   // 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 111; }   // 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -133,6 +133,25 @@ int adm_sched_step_thresholded(const float* x, const float* eps, const float* no
   SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
   p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
   return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream);
+}
+
+int adm_sched_threshold_pred(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step, int lo,
+                             int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W, void* stream,
+                             int prediction) {
+  ADM_REQUIRE(x && eps && coef_table && scale_out, "sched_threshold_pred: null argument");
+  return launch_sched_threshold(x, eps, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W,
+                                (hipStream_t)stream, prediction);
+}
+
+int adm_sched_step_pred(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
+                        const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask, int n_mask_steps,
+                        int mask_start, int mask_end, int B, int C, int H, int W, void* stream, int lo, int hi, float w,
+                        float max_value, float* scale, int prediction) {
+  ADM_REQUIRE(x && eps && out && coef_table, "sched_step_pred: null argument");
+  SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
+  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
+  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);
 }
 
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

@@ -6,6 +6,12 @@ using namespace adm;
 
 extern "C" {
 
+int adm_noise_and_velocity(const float* x0, const float* noise, const float* sa, const float* sb, float* noisy_out,
+                           float* velocity_out, int B, long P, void* stream) {
+  ADM_REQUIRE(x0 && noise && sa && sb && noisy_out && velocity_out, "noise_and_velocity: null argument");
+  return launch_noise_and_velocity(x0, noise, sa, sb, noisy_out, velocity_out, B, P, (hipStream_t)stream);
+}
+
 int adm_groupnorm_stats_ex(const float* x1, int C1, const float* x2, int C2, int N, int HW, int groups, float eps,
                            const float* gamma, const float* beta, float* scale, float* shift, float* mean_rstd,
                            void* stream) {

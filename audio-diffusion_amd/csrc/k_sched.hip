@@ -13,13 +13,34 @@
 //                    over an LDS histogram of the bit pattern of |x0|; x0 is recomputed from x and eps in every pass (8 B/elem per pass,
 //                    3 passes + 1 when the two ranks straddle two distinct values: 24-32 B/elem, L2-resident), nothing but the B scales
 //                    goes to global memory.
+// What the model predicts (PRED_EPSILON / PRED_SAMPLE / PRED_V) is a second template parameter of the SAME step body and of the selection's
+// key: sched_step_kernel<MODE> and sched_threshold_kernel are the epsilon instantiations under their old names, sched_step_pred_kernel
+// <MODE, PRED> and sched_threshold_pred_kernel<PRED> the sample / v_prediction ones (SCHED_PLAIN and SCHED_THRESH; the multistep step is
+// epsilon only). Same traffic: the parameterisation only changes the few flops that turn (x, model output) into (x0, eps).
 #include "adm_kernels.h"
 
 namespace adm {
 
-// the x0 prediction: ONE helper for the step kernels and the selection, so that both see the same bits
-__device__ __forceinline__ float sched_x0(float x, float e, const adm_sched_coef& c) {
-  return (x - c.sqrt_beta * e) / c.sqrt_alpha;
+// the x0 prediction: ONE helper for the step kernels and the selection, so that both see the same bits. o is the model output:
+//   PRED_EPSILON  x0 = (x - sb*o) / sa      PRED_SAMPLE  x0 = o      PRED_V  x0 = sa*x - sb*o
+// The v form is written as one product and one fused multiply-add, so that its bits depend on no contraction setting and on no
+// inlining context (two products and a difference can be contracted two ways). At the zero-SNR row (sa = 0, sb = 1) it is -o exactly.
+template <int PRED>
+__device__ __forceinline__ float sched_x0(float x, float o, const adm_sched_coef& c) {
+  if (PRED == PRED_SAMPLE) return o;
+  if (PRED == PRED_V) return fmaf(c.sqrt_alpha, x, -__fmul_rn(c.sqrt_beta, o));
+  return (x - c.sqrt_beta * o) / c.sqrt_alpha;
+}
+
+// the noise prediction that k_eps multiplies, from the x0 of sched_x0 BEFORE its clamp or threshold (diffusers does the same):
+//   PRED_EPSILON  e = o      PRED_SAMPLE  e = (x - sa*x0) / sb      PRED_V  e = sa*o + sb*x
+// At sa = 0, sb = 1 both new forms give e = x exactly. The sample form divides by sb: a row with sb = 0 (alphas_cumprod == 1, which only
+// trained betas that start with zeros can make) is out of contract here and refused by the schedulers on the host.
+template <int PRED>
+__device__ __forceinline__ float sched_eps(float x, float o, float x0, const adm_sched_coef& c) {
+  if (PRED == PRED_SAMPLE) return fmaf(-c.sqrt_alpha, x0, x) / c.sqrt_beta;
+  if (PRED == PRED_V) return fmaf(c.sqrt_alpha, o, __fmul_rn(c.sqrt_beta, x));
+  return o;
 }
 
 __device__ __forceinline__ unsigned char quant_u8(float v) {
@@ -39,9 +60,12 @@ __device__ __forceinline__ unsigned pack_u8x4(float a, float b, float c, float d
 //                    hist = m0 (always, and before the mask: the history is the model's x0).
 //                    hist is read ONLY where k_hist != 0: the first row of a run has k_hist == 0 and finds the buffer uninitialised
 //                    (0 * NaN must not reach the output). Each lane reads and rewrites its own elements of hist.
+// PRED: what p.eps holds (the model output o); e below is sched_eps of it, the model output itself for PRED_EPSILON.
 // out may alias x.
-template <int MODE>
-__global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p) {
+// first, stride: the lane's first float4 and the grid's stride, which the kernel works out itself (a launch-geometry builtin is only
+// folded against the kernel's launch bounds where the kernel reads it).
+template <int MODE, int PRED>
+__device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const long first, const long stride) {
   const int s = p.step_dev ? *p.step_dev : p.step;
   const adm_sched_coef c = p.table[s];
   const float k_hist = MODE == SCHED_MULTISTEP ? p.k_hist_table[s] : 0.f;
@@ -49,8 +73,7 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p
   const bool use_noise = p.noise != nullptr && c.k_noise != 0.f;
   const float* noise = p.noise + (long)s * p.noise_step_stride;  // per-step slice of a (n_steps,B,C,H,W) noise tensor (0: single step)
   unsigned char* u8 = p.u8_step >= 0 && s != p.u8_step ? nullptr : p.u8;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n4; i += stride) {
+  for (long i = first; i < p.n4; i += stride) {
     const float4 xv = reinterpret_cast<const float4*>(p.x)[i];
     const float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
     float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -59,8 +82,9 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p
     float th = 0.f;
     if (MODE == SCHED_THRESH) th = p.scale[(i * 4) / p.per_sample];  // W % 4 == 0: a float4 never straddles two samples
     float4 mv;  // x0 of this step, clamped: the next step's history
-    auto one = [&](float x, float e, float nz, float h, float& m0) {
-      float x0 = sched_x0(x, e, c);
+    auto one = [&](float x, float o, float nz, float h, float& m0) {
+      float x0 = sched_x0<PRED>(x, o, c);
+      const float e = sched_eps<PRED>(x, o, x0, c);
       if (MODE == SCHED_THRESH) x0 = fminf(fmaxf(x0, -th), th) / th;
       else if (c.clip >= 0.f) x0 = fminf(fmaxf(x0, -c.clip), c.clip);
       float prev = c.k_x0 * x0 + c.k_x * x;
@@ -94,6 +118,17 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p
   }
 }
 
+template <int MODE>
+__global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p) {
+  sched_step_body<MODE, PRED_EPSILON>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+template <int MODE, int PRED>
+__global__ void __launch_bounds__(256) sched_step_pred_kernel(const SchedStepParams p) {
+  static_assert(MODE != SCHED_MULTISTEP && PRED != PRED_EPSILON, "the sample / v_prediction steps: plain and thresholded only");
+  sched_step_body<MODE, PRED>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
 // ---- dynamic threshold: exact per-sample order statistics of |x0| ---------------------------------------------------------------------
 // Key = bit pattern of |x0| (non-negative floats order as unsigned integers; -0.0 becomes 0; NaN patterns order last). Three passes select
 // the key of rank lo digit by digit, most significant first: each pass histograms, in LDS, one digit of the keys that match the digits
@@ -102,8 +137,9 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p
 // per sample and no global scratch: nothing to reset between replays, and a sample's result cannot depend on its batch.
 constexpr int kThreshThreads = 1024, kThreshBins = 2048;
 
+template <int PRED>
 __device__ __forceinline__ unsigned thresh_key(float x, float e, const adm_sched_coef& c) {
-  return __float_as_uint(sched_x0(x, e, c)) & 0x7fffffffu;
+  return __float_as_uint(sched_x0<PRED>(x, e, c)) & 0x7fffffffu;
 }
 
 __device__ __forceinline__ float thresh_bits_to_float(unsigned u) {
@@ -114,7 +150,7 @@ __device__ __forceinline__ float thresh_bits_to_float(unsigned u) {
 
 // One sweep of a sample: f(key) for the key of every element. Four float4 pairs per lane are loaded before any is used: with one workgroup
 // per sample (a single CU when B = 1) the sweep is bound by load latency, not by bandwidth.
-template <class F>
+template <int PRED, class F>
 __device__ __forceinline__ void thresh_sweep(const float4* __restrict__ xp, const float4* __restrict__ ep, int n4, int tid,
                                              const adm_sched_coef& c, F f) {
   for (int i0 = tid; i0 < n4; i0 += 4 * kThreshThreads) {
@@ -127,8 +163,8 @@ __device__ __forceinline__ void thresh_sweep(const float4* __restrict__ xp, cons
     ADM_UNROLL
     for (int u = 0; u < 4; ++u) {
       if (i0 + u * kThreshThreads < n4) {
-        f(thresh_key(xv[u].x, ev[u].x, c)); f(thresh_key(xv[u].y, ev[u].y, c));
-        f(thresh_key(xv[u].z, ev[u].z, c)); f(thresh_key(xv[u].w, ev[u].w, c));
+        f(thresh_key<PRED>(xv[u].x, ev[u].x, c)); f(thresh_key<PRED>(xv[u].y, ev[u].y, c));
+        f(thresh_key<PRED>(xv[u].z, ev[u].z, c)); f(thresh_key<PRED>(xv[u].w, ev[u].w, c));
       }
     }
   }
@@ -155,7 +191,8 @@ __device__ __forceinline__ void thresh_find_bin(const unsigned* hist, int nbins,
   }
 }
 
-__global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
+template <int PRED>
+__device__ __forceinline__ void sched_threshold_body(
     const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
     const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
     float* __restrict__ scale) {
@@ -174,7 +211,7 @@ __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
     const int up = pass == 0 ? 31 : shift + 10;                // the digits above this one are fixed by `prefix`
     for (int j = tid; j < nbins; j += kThreshThreads) hist[j] = 0;
     __syncthreads();
-    thresh_sweep(xp, ep, n4, tid, c, [&](unsigned key) {
+    thresh_sweep<PRED>(xp, ep, n4, tid, c, [&](unsigned key) {
       if ((key >> up) == (prefix >> up)) atomicAdd(&hist[(key >> shift) & (unsigned)(nbins - 1)], 1u);
     });
     __syncthreads();
@@ -190,7 +227,7 @@ __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
     if (tid == 0) hist[0] = 0;
     __syncthreads();
     unsigned m = 0xffffffffu;
-    thresh_sweep(xp, ep, n4, tid, c, [&](unsigned key) {
+    thresh_sweep<PRED>(xp, ep, n4, tid, c, [&](unsigned key) {
       if (key > prefix && key < m) m = key;
     });
     for (int d = 32; d >= 1; d >>= 1) {
@@ -210,6 +247,21 @@ __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
     const float q = w < 0.5f ? fmaf(w, d, a) : fmaf(-d, __fadd_rn(1.f, -w), b);
     scale[blockIdx.x] = fminf(fmaxf(q, 1.f), max_value);
   }
+}
+
+__global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
+    const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
+    const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
+    float* __restrict__ scale) {
+  sched_threshold_body<PRED_EPSILON>(x, eps, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
+}
+
+template <int PRED>
+__global__ void __launch_bounds__(kThreshThreads) sched_threshold_pred_kernel(
+    const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
+    const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
+    float* __restrict__ scale) {
+  sched_threshold_body<PRED>(x, eps, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
 }
 
 __global__ void step_advance_kernel(int* step_dev) { *step_dev += 1; }
@@ -234,6 +286,9 @@ __global__ void __launch_bounds__(256) encode_step_kernel(float* x, const float*
   }
 }
 
+// sa*x0 + sb*noise: ONE expression for add_noise_kernel and noise_and_velocity_kernel, whose `noisy` must equal add_noise's bit for bit
+__device__ __forceinline__ float noisy_of(float a, float x, float s, float n) { return a * x + s * n; }
+
 __global__ void __launch_bounds__(256) add_noise_kernel(const float* __restrict__ x0, long x0_bstride,
                                                         const float* __restrict__ noise,
                                                         const float* __restrict__ sa, const float* __restrict__ sb,
@@ -245,7 +300,25 @@ __global__ void __launch_bounds__(256) add_noise_kernel(const float* __restrict_
   float4* op = reinterpret_cast<float4*>(out) + ((long)b * N + n) * P4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < P4; i += (long)gridDim.x * blockDim.x) {
     const float4 xv = xp[i], nv = np[i];
-    op[i] = make_float4(a * xv.x + s * nv.x, a * xv.y + s * nv.y, a * xv.z + s * nv.z, a * xv.w + s * nv.w);
+    op[i] = make_float4(noisy_of(a, xv.x, s, nv.x), noisy_of(a, xv.y, s, nv.y), noisy_of(a, xv.z, s, nv.z), noisy_of(a, xv.w, s, nv.w));
+  }
+}
+
+// Training prologue of a v-model: per sample b, noisy = sa[b]*x0 + sb[b]*noise (add_noise's per-sample form) and the regression target
+// velocity = sa[b]*noise - sb[b]*x0, from one read of x0 and noise: 16 B/elem where two add_noise passes would move 24.
+__global__ void __launch_bounds__(256) noise_and_velocity_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                 const float* __restrict__ sa, const float* __restrict__ sb,
+                                                                 float* __restrict__ noisy, float* __restrict__ velocity, long P4) {
+  const int b = blockIdx.y;
+  const float a = sa[b], s = sb[b];
+  const float4* xp = reinterpret_cast<const float4*>(x0) + (long)b * P4;
+  const float4* np = reinterpret_cast<const float4*>(noise) + (long)b * P4;
+  float4* yp = reinterpret_cast<float4*>(noisy) + (long)b * P4;
+  float4* vp = reinterpret_cast<float4*>(velocity) + (long)b * P4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < P4; i += (long)gridDim.x * blockDim.x) {
+    const float4 xv = xp[i], nv = np[i];
+    yp[i] = make_float4(noisy_of(a, xv.x, s, nv.x), noisy_of(a, xv.y, s, nv.y), noisy_of(a, xv.z, s, nv.z), noisy_of(a, xv.w, s, nv.w));
+    vp[i] = make_float4(a * nv.x - s * xv.x, a * nv.y - s * xv.y, a * nv.z - s * xv.z, a * nv.w - s * xv.w);
   }
 }
 
@@ -263,20 +336,31 @@ static inline int ew_grid(long n4) {
 }
 
 int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
-                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st) {
+                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st, int pred) {
   const long per_sample = (long)C * H * W;
   ADM_REQUIRE(B > 0 && W % 4 == 0, "sched_threshold: W must be a multiple of 4");
   ADM_REQUIRE(per_sample > 0 && per_sample < (1L << 31), "sched_threshold: C*H*W must be below 2^31");
   ADM_REQUIRE(lo >= 0 && hi >= lo && hi - lo <= 1 && hi < per_sample, "sched_threshold: need 0 <= lo <= hi <= C*H*W - 1 and hi - lo <= 1");
   ADM_REQUIRE(w >= 0.f && w < 1.f, "sched_threshold: the interpolation weight must be in [0, 1)");
   ADM_REQUIRE(max_value >= 1.f, "sched_threshold: max_value must be >= 1");
-  ADM_LAUNCH(sched_threshold_kernel, dim3(B), dim3(kThreshThreads), 0, st, x, eps, table, step_dev, step, per_sample,
-             (unsigned)lo, (unsigned)hi, w, max_value, scale);
+  ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_threshold: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  const dim3 grid(B), block(kThreshThreads);
+  if (pred == PRED_SAMPLE)
+    ADM_LAUNCH(sched_threshold_pred_kernel<PRED_SAMPLE>, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo,
+               (unsigned)hi, w, max_value, scale);
+  else if (pred == PRED_V)
+    ADM_LAUNCH(sched_threshold_pred_kernel<PRED_V>, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo,
+               (unsigned)hi, w, max_value, scale);
+  else
+    ADM_LAUNCH(sched_threshold_kernel, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo, (unsigned)hi, w,
+               max_value, scale);
   return ADM_CHECK_LAUNCH();
 }
 
 // SCHED_THRESH: selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written
-int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st) {
+int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int pred) {
+  ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_step: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  ADM_REQUIRE(pred == PRED_EPSILON || mode != SCHED_MULTISTEP, "sched_multistep: prediction must be 0 (the multistep step is epsilon only)");
   SchedStepParams p = in;
   p.per_sample = (long)p.C * p.H * p.W;
   p.n4 = p.per_sample * p.B / 4;
@@ -285,8 +369,10 @@ int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st) {
   if (mode == SCHED_THRESH) {
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_thresholded: mask path requires C == 1 (as in the reference)");
     ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,
-                                   p.W, st));
-    ADM_LAUNCH(sched_step_kernel<SCHED_THRESH>, grid, block, 0, st, p);
+                                   p.W, st, pred));
+    if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_SAMPLE>), grid, block, 0, st, p);
+    else if (pred == PRED_V) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_V>), grid, block, 0, st, p);
+    else ADM_LAUNCH(sched_step_kernel<SCHED_THRESH>, grid, block, 0, st, p);
   } else if (mode == SCHED_MULTISTEP) {
     ADM_REQUIRE(p.W % 4 == 0, "sched_multistep: W must be a multiple of 4");
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_multistep: mask path requires C == 1 (as in the reference)");
@@ -295,7 +381,9 @@ int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st) {
     ADM_REQUIRE(mode == SCHED_PLAIN, "sched_step: unknown mode");
     ADM_REQUIRE(p.W % 4 == 0, "sched_step: W must be a multiple of 4");
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
-    ADM_LAUNCH(sched_step_kernel<SCHED_PLAIN>, grid, block, 0, st, p);
+    if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_SAMPLE>), grid, block, 0, st, p);
+    else if (pred == PRED_V) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_V>), grid, block, 0, st, p);
+    else ADM_LAUNCH(sched_step_kernel<SCHED_PLAIN>, grid, block, 0, st, p);
   }
   return ADM_CHECK_LAUNCH();
 }
@@ -319,6 +407,15 @@ int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const
   if (g > 256) g = 256;
   ADM_LAUNCH(add_noise_kernel, dim3((unsigned)g, N, B), dim3(256), 0, st, x0, x0_bstride, noise, sa, sb, cb, cn, out, N,
              P / 4);
+  return ADM_CHECK_LAUNCH();
+}
+
+int launch_noise_and_velocity(const float* x0, const float* noise, const float* sa, const float* sb, float* noisy, float* velocity,
+                              int B, long P, hipStream_t st) {
+  ADM_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 4 == 0, "noise_and_velocity: need 0 < B <= 65535 and P a positive multiple of 4");
+  long g = (P / 4 + 255) / 256;
+  if (g > 256) g = 256;
+  ADM_LAUNCH(noise_and_velocity_kernel, dim3((unsigned)g, B), dim3(256), 0, st, x0, noise, sa, sb, noisy, velocity, P / 4);
   return ADM_CHECK_LAUNCH();
 }
 

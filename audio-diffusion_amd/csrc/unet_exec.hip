@@ -342,6 +342,7 @@ struct LoopArgs {
   float* x; int B; int n_steps; const float* step_noise; const float* mask; int mask_start, mask_end;
   uint8_t* u8; int mode; const float* k_hist_host;
   int th_lo = 0, th_hi = 0; float th_w = 0.f, th_max = 1.f;   // SCHED_THRESH: the two ranks, their weight and sample_max_value
+  int pred = PRED_EPSILON;                                    // what the model output is: chooses the step (and selection) kernel
 };
 
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
@@ -358,7 +359,7 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
     p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
     p.lo = a.th_lo; p.hi = a.th_hi; p.w = a.th_w; p.max_value = a.th_max; p.scale = h->scale_buf;
     p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
-    ADM_TRY(launch_sched_step(p, a.mode, st));
+    ADM_TRY(launch_sched_step(p, a.mode, st, a.pred));
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
   return 0;
@@ -392,7 +393,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
     std::vector<uint64_t> key = {(uint64_t)a.x, (uint64_t)a.B, (uint64_t)a.n_steps, (uint64_t)a.step_noise,
                                  (uint64_t)a.mask, (uint64_t)a.mask_start, (uint64_t)a.mask_end, (uint64_t)a.u8,
                                  (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
-                                 (uint64_t)h->net.ctx_S};
+                                 (uint64_t)h->net.ctx_S, (uint64_t)a.pred};   // (pred: the kernel itself is baked into the captured node)
     if (a.mode == SCHED_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
     if (a.mode == SCHED_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
       uint32_t wb, mb;
@@ -696,6 +697,18 @@ int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop_thresholded: bad argument");
   LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_THRESH, nullptr};
   a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value;
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+}
+
+int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, const float* step_noise,
+                         const float* mask, int mask_start, int mask_end, uint8_t* u8_out, int use_graph, void* stream, int lo,
+                         int hi, float w, float max_value, int thresholded, int prediction) {
+  ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop_pred: bad argument");
+  ADM_REQUIRE(prediction >= PRED_EPSILON && prediction <= PRED_V,
+              "sample_loop_pred: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, thresholded ? SCHED_THRESH : SCHED_PLAIN, nullptr};
+  if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
+  a.pred = prediction;
   return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 

@@ -80,13 +80,20 @@ class Trainer:
 
     def step(self, noise_scheduler, clean, noise, timesteps, encoding=None, last_batch=False):
         model, ema, grads, flat, scaler = self.model, self.ema, self.grads, self.flat, self.scaler
-        noisy = noise_scheduler.add_noise(clean.contiguous(), noise, timesteps)
+        # the regression target follows the scheduler's prediction_type: the noise, the clean sample, or the velocity, which comes with
+        # `noisy` out of one fused kernel (ops.noise_and_velocity) instead of add_noise
+        kind = noise_scheduler.config.prediction_type
+        if kind == "v_prediction":
+            noisy, target = noise_scheduler.add_noise_and_velocity(clean.contiguous(), noise, timesteps)
+        else:
+            noisy = noise_scheduler.add_noise(clean.contiguous(), noise, timesteps)
+            target = noise if kind == "epsilon" else clean.contiguous()
         self.reducer.begin_step()
         ls = scaler.get_scale() if scaler is not None else 1.0
         if encoding is not None:                                       # :254-255
-            loss = model.train_step(noisy, timesteps, noise, encoding, loss_scale=ls)
+            loss = model.train_step(noisy, timesteps, target, encoding, loss_scale=ls)
         else:
-            loss = model.train_step(noisy, timesteps, noise, loss_scale=ls)
+            loss = model.train_step(noisy, timesteps, target, loss_scale=ls)
         if self.accum.add(last_batch=last_batch):                      # accelerator.sync_gradients
             self.reducer.start()
             self.reducer.finish()
@@ -176,7 +183,8 @@ def main(args):
                             up_block_types=("UpBlock2D", "AttnUpBlock2D") + ("UpBlock2D",) * 4).init_random(args.seed)
         mel = Mel(x_res=resolution[1], y_res=resolution[0], hop_length=args.hop_length, sample_rate=args.sample_rate,
                   n_fft=args.n_fft)
-    noise_scheduler = (DDPMScheduler if args.scheduler == "ddpm" else DDIMScheduler)(num_train_timesteps=args.num_train_steps)
+    noise_scheduler = (DDPMScheduler if args.scheduler == "ddpm" else DDIMScheduler)(num_train_timesteps=args.num_train_steps,
+                                                                                   prediction_type=args.prediction_type)
 
     n_local = len(images) // world
     # len(train_dataloader) of the reference (:91, DataLoader default drop_last=False): the last batch may be partial
@@ -290,6 +298,8 @@ def parse_args(argv=None):
     parser.add_argument("--start_epoch", type=int, default=0)
     parser.add_argument("--num_train_steps", type=int, default=1000)
     parser.add_argument("--scheduler", type=str, default="ddpm", help="ddpm or ddim")
+    parser.add_argument("--prediction_type", type=str, default="epsilon", choices=("epsilon", "sample", "v_prediction"),
+                        help="what the model is trained to predict; saved in scheduler/scheduler_config.json")
     parser.add_argument("--vae", type=str, default=None)
     parser.add_argument("--encodings", type=str, default=None)
     # additions (not in the reference)

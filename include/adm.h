@@ -158,10 +158,39 @@ int adm_sched_step_thresholded(const float* x, const float* eps, const float* no
                                int B, int C, int H, int W, void* stream,
                                int lo, int hi, float w, float max_value, float* scale);
 
+/* Models that predict the clean sample or the velocity instead of the noise (diffusers' prediction_type "sample" / "v_prediction", Salimans &
+ * Ho 2022; adm_version() >= 111). `prediction`: 0 epsilon, 1 sample, 2 v_prediction; `eps` is then the model output o, and with
+ * sa = sqrt_alpha, sb = sqrt_beta of the row
+ *   epsilon       x0 = (x - sb*o) / sa     e = o
+ *   sample        x0 = o                   e = (x - sa*x0) / sb
+ *   v_prediction  x0 = sa*x - sb*o         e = sa*o + sb*x
+ * e is formed from x0 BEFORE the clamp or the threshold; everything after is adm_sched_step's:
+ *   x0 = clamp(x0) (static or dynamic),  prev = k_x0*x0 + k_x*x + k_eps*e + k_noise*noise,  mask overwrite, u8.
+ * The same eight adm_sched_coef fields serve the three types. On a zero-terminal-SNR row (sa = 0, sb = 1) the two new forms stay finite:
+ * x0 = -o, e = x (v_prediction) and x0 = o, e = x (sample); the epsilon form divides by zero there.
+ * adm_sched_threshold_pred: adm_sched_threshold with |x0| of the given type (for `sample` that is |o|, at any sa).
+ * adm_sched_step_pred: scale == NULL: adm_sched_step (the row's static clip; lo, hi, w, max_value are ignored); otherwise
+ * adm_sched_step_thresholded. With prediction == 0 both run the kernels of the entry points they are named after, bit for bit. */
+int adm_sched_threshold_pred(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step,
+                             int lo, int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W, void* stream,
+                             int prediction);
+int adm_sched_step_pred(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
+                        const adm_sched_coef* coef_table, const int* step_dev, int step,
+                        const float* mask, int n_mask_steps, int mask_start, int mask_end,
+                        int B, int C, int H, int W, void* stream,
+                        int lo, int hi, float w, float max_value, float* scale, int prediction);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
                   int cb, int cn, float* out, int B, int N, long P, void* stream);
+
+/* Training prologue of a v_prediction model (adm_version() >= 111): per sample b over P elements, with sa, sb device arrays of B floats,
+ *   noisy_out[b][p]    = sa[b]*x0[b][p] + sb[b]*noise[b][p]      (bit-identical to adm_add_noise with cb = 1, cn = 0, N = 1)
+ *   velocity_out[b][p] = sa[b]*noise[b][p] - sb[b]*x0[b][p]      (the regression target; diffusers' get_velocity)
+ * One read of x0 and noise, two writes. P % 4 == 0. */
+int adm_noise_and_velocity(const float* x0, const float* noise, const float* sa, const float* sb, float* noisy_out,
+                           float* velocity_out, int B, long P, void* stream);
 
 /* (x/2+0.5).clamp(0,1)*255 round-half-even -> u8 (pipeline_audio_diffusion.py:192-194). */
 int adm_dequant_u8(const float* x, uint8_t* out, long n, void* stream);
@@ -417,6 +446,13 @@ int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_co
 int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                                 const float* step_noise, const float* mask, int mask_start, int mask_end,
                                 uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value);
+/* adm_sample_loop / adm_sample_loop_thresholded for a model of the given `prediction` (0 epsilon, 1 sample, 2 v_prediction; adm_sched_step_pred;
+ * adm_version() >= 111). thresholded == 0: the static clamp, and lo, hi, w, max_value are ignored. The prediction type is part of the captured
+ * graph's key: one handle may alternate between types. */
+int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
+                         const float* step_noise, const float* mask, int mask_start, int mask_end,
+                         uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
+                         int thresholded, int prediction);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,

@@ -1,0 +1,100 @@
+"""scripts/train_unet.py --prediction_type v_prediction end to end on the emulator: one epoch on the synthetic 16 x 16 dataset trains
+against the velocity (`ops.noise_and_velocity`: `noisy` and the target from one kernel), the saved scheduler_config.json carries the type,
+and the reloaded pipeline samples through the loop of that type (`adm_sample_loop_pred`)."""
+import importlib.util
+import json
+import os
+
+import pytest
+import torch
+
+from native_backend import select
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TINY = dict(sample_size=(16, 16), in_channels=1, out_channels=1, layers_per_block=1, block_out_channels=(32, 64),
+            down_block_types=("DownBlock2D", "AttnDownBlock2D"), up_block_types=("AttnUpBlock2D", "UpBlock2D"))
+MEL = dict(x_res=16, y_res=16, hop_length=64, n_fft=256, n_iter=2, sample_rate=4000)
+
+
+def _script(name):
+    spec = importlib.util.spec_from_file_location("adm_" + name, os.path.join(ROOT, "audio-diffusion_amd", "scripts", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("kind,scheduler", [("v_prediction", "ddpm"), ("sample", "ddim")])
+def test_training_script_with_a_prediction_type(kind, scheduler, tmp_path, monkeypatch):
+    select("emu")
+    from audiodiffusion import AudioDiffusionPipeline, DDPMScheduler, Mel, UNet2DModel
+    from audiodiffusion import _native as N
+    from audiodiffusion import ops
+    start = UNet2DModel(**TINY).init_random(3)
+    AudioDiffusionPipeline(None, start, Mel(**MEL), DDPMScheduler()).save_pretrained(str(tmp_path / "start"))
+    w0 = {k: v.clone() for k, v in start.state_dict().items()}
+    tr = _script("train_unet")
+    losses, targets, fused, added, per_step = [], [], [], [], []
+    step, train_step, nav, add_noise = tr.Trainer.step, UNet2DModel.train_step, ops.noise_and_velocity, ops.add_noise
+
+    def spy_step(self, noise_scheduler, clean, noise, timesteps, *a, **k):
+        targets.append((noise_scheduler, clean.clone(), noise.clone(), timesteps.clone()))
+        before = (len(fused), len(added))
+        loss = step(self, noise_scheduler, clean, noise, timesteps, *a, **k)
+        per_step.append((len(fused) - before[0], len(added) - before[1]))    # the kernels Trainer.step itself launched
+        losses.append(float(loss))
+        return loss
+
+    def spy_train_step(self, noisy, timesteps, target, *a, **k):
+        targets[-1] += (noisy.clone(), target.clone())
+        return train_step(self, noisy, timesteps, target, *a, **k)
+
+    def spy_nav(*a):
+        fused.append(1)
+        return nav(*a)
+
+    monkeypatch.setattr(tr.Trainer, "step", spy_step)
+    monkeypatch.setattr(UNet2DModel, "train_step", spy_train_step)
+    def spy_add_noise(*a, **k):
+        added.append(1)
+        return add_noise(*a, **k)
+
+    monkeypatch.setattr(ops, "noise_and_velocity", spy_nav)
+    monkeypatch.setattr(ops, "add_noise", spy_add_noise)
+    tr.main(tr.parse_args(["--from_pretrained", str(tmp_path / "start"), "--dataset_name", "synthetic", "--resolution", "16",
+                           "--synthetic_size", "4", "--output_dir", str(tmp_path / "out"), "--train_batch_size", "2", "--num_epochs", "1",
+                           "--save_model_epochs", "1", "--lr_warmup_steps", "1", "--learning_rate", "1e-3", "--scheduler", scheduler,
+                           "--prediction_type", kind, "--hop_length", "64", "--sample_rate", "4000", "--n_fft", "256"]))
+    assert len(losses) == 2 and all(l == l and abs(l) != float("inf") for l in losses), losses
+    # the target is what the type says, and `noisy` is add_noise's
+    for sched, clean, noise, ts, noisy, target in targets:
+        assert sched.config.prediction_type == kind
+        assert torch.equal(noisy, sched.add_noise(clean.contiguous(), noise, ts))
+        want = clean if kind == "sample" else sched.get_velocity(clean.contiguous(), noise, ts)
+        assert torch.equal(target, want) and not torch.equal(target, noise)
+    # v: ONE fused call per training step and no add_noise; sample: one add_noise and no fused call (counted inside Trainer.step only:
+    # the verification loop above goes through the same ops)
+    assert per_step == [(1, 0)] * 2 if kind == "v_prediction" else per_step == [(0, 1)] * 2, per_step
+    d = json.load(open(tmp_path / "out" / "scheduler" / "scheduler_config.json"))
+    assert d["prediction_type"] == kind
+    pipe = AudioDiffusionPipeline.from_pretrained(str(tmp_path / "out"))
+    pipe.set_progress_bar_config(disable=True)
+    assert pipe.scheduler.config.prediction_type == kind and pipe.scheduler.prediction == {"sample": 1, "v_prediction": 2}[kind]
+    w1 = pipe.unet.state_dict()
+    changed = sum(float((w1[k] - w0[k]).abs().max()) > 0 for k in w0)
+    assert changed >= 0.9 * len(w0), f"only {changed} of {len(w0)} tensors moved"
+    assert all(torch.isfinite(v).all() for v in w1.values())
+    # the reloaded pipeline samples through the loop of its type
+    calls = []
+    real = N.lib().adm_sample_loop_pred
+
+    class _Lib:
+        def __getattr__(self, name):
+            if name == "adm_sample_loop_pred":
+                return lambda *a: (calls.append(a[-1]), real(*a))[1]
+            return getattr(real_lib, name)
+    real_lib = N.lib()
+    monkeypatch.setattr(N, "lib", lambda: _Lib())
+    noise = torch.randn(1, 1, 16, 16, generator=torch.Generator().manual_seed(0))
+    images, floats = pipe(batch_size=1, steps=3, noise=noise, step_noise=torch.randn(3, 1, 1, 16, 16), audio=False, return_float=True)
+    assert calls and set(calls) == {pipe.scheduler.prediction}
+    assert images[0].size == (16, 16) and bool(torch.isfinite(floats).all())
