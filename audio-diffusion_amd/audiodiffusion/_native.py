@@ -95,6 +95,10 @@ _SIGS = {
                                  [C.c_void_p, C.c_int]),
     "adm_sched_step_pred": (C.c_int, [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 +
                             [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int]),
+    "adm_sched_threshold_guided": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.c_float, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int]),
+    "adm_sched_step_guided": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p] + [C.c_int] * 7 +
+                              [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int]),
     "adm_noise_and_velocity": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_long, C.c_void_p]),
     "adm_add_noise": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                 C.c_int, C.c_int, C.c_long, C.c_void_p]),
@@ -151,6 +155,9 @@ _SIGS = {
     "adm_sample_loop_pred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_float, C.c_float, C.c_int, C.c_int]),
+    "adm_sample_loop_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), c_float_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_float]),
     "adm_encode_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_int, C.c_void_p]),
 }
 # entry points added by later translation units (k_mel.hip); bound when present in the header AND the library

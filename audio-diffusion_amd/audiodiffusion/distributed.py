@@ -24,10 +24,23 @@ def global_noise(shape, seed, steps_with_noise=0):
     return x, sn
 
 
+def _rows(t, lo, hi, global_batch, name, broadcast=False):
+    """Rows [lo:hi] of a GLOBAL per-sample tensor. broadcast: a leading 1 is shared by every row and passed on as it is (the pipeline
+    broadcasts a negative encoding, and only that)."""
+    if t is None or (broadcast and t.shape[0] == 1):
+        return t
+    if t.shape[0] != global_batch:
+        raise ValueError(f"{name} has {t.shape[0]} rows for a global batch of {global_batch}")
+    return t[lo:hi].contiguous()
+
+
 @torch.no_grad()
-def sample_sharded(pipe, global_batch, steps=None, seed=42, eta=0.0, gather=True, group=None):
+def sample_sharded(pipe, global_batch, steps=None, seed=42, eta=0.0, gather=True, group=None, encoding=None, guidance_scale=None,
+                   negative_encoding=None):
     """Returns (images_u8, local_slice): uint8 tensor (global_batch, H, W) on every rank when `gather`, else the
-    local shard; `local_slice` = (lo, hi) rows owned by this rank."""
+    local shard; `local_slice` = (lo, hi) rows owned by this rank. encoding and negative_encoding are GLOBAL tensors
+    (global_batch, seq, dim), row-sliced per rank like the noise (negative_encoding may have a leading 1 instead: broadcast);
+    guidance_scale as in `AudioDiffusionPipeline.__call__`. The row counts are checked before any rank samples."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     steps = steps or pipe.get_default_steps()
@@ -43,8 +56,11 @@ def sample_sharded(pipe, global_batch, steps=None, seed=42, eta=0.0, gather=True
     if n_noise:
         it = iter(sn)
         step_noise = [next(it)[lo:hi].to(dev) if r["k_noise"] != 0.0 else None for r in rows]
+    enc = _rows(encoding, lo, hi, global_batch, "encoding")          # (on every rank, rows or not: all raise, or none)
+    neg = _rows(negative_encoding, lo, hi, global_batch, "negative_encoding", broadcast=True)
     if hi > lo:
-        _, u8 = pipe._denoise(x[lo:hi].contiguous().to(dev), 0, eta, None, None, 0, 0, step_noise=step_noise)
+        _, u8 = pipe._denoise(x[lo:hi].contiguous().to(dev), 0, eta, None, None, 0, 0, step_noise=step_noise,
+                              encoding=enc, guidance_scale=guidance_scale, negative_encoding=neg)
         u8 = u8.reshape(hi - lo, H, W)
     else:      # more ranks than rows (global_batch < world * per): this rank owns nothing, and still takes part in the gather
         u8 = torch.zeros((0, H, W), dtype=torch.uint8, device=dev)

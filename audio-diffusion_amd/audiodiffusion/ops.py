@@ -34,15 +34,33 @@ def threshold_ranks(n, ratio):
 PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}   # the C-ABI's `prediction`
 
 
-def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None, prediction=0):
+def _guidance(eps, uncond, guidance_scale):
+    """Classifier-free guidance arguments: both given, or neither. -> True when the guided entry points are to run."""
+    if (uncond is None) != (guidance_scale is None):
+        raise ValueError("classifier-free guidance needs both `uncond` and `guidance_scale` (or neither)")
+    if uncond is None:
+        return False
+    _f32(uncond)
+    assert uncond.shape == eps.shape and uncond.device == eps.device
+    return True
+
+
+def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None, prediction=0, uncond=None,
+                    guidance_scale=None):
     """Per-sample dynamic threshold s_b = clamp(quantile(|x0_b|, ratio), 1, max_value) of x0 = (x - sqrt_beta*eps) / sqrt_alpha
     (csrc/k_sched.hip `sched_threshold_kernel`: an exact radix select on the device, equal to torch.quantile to the bit). -> (B,) fp32.
     prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model and x0 is formed accordingly
-    (`adm_sched_threshold_pred`)."""
+    (`adm_sched_threshold_pred`). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional output and x0 is that of
+    o = uncond + guidance_scale * (eps - uncond) (`adm_sched_threshold_guided`)."""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
     lo, hi, w = threshold_ranks(Cc * H * W, ratio)
     out = torch.empty((B,), dtype=torch.float32, device=x.device) if out is None else out
+    if _guidance(eps, uncond, guidance_scale):
+        N.check(N.lib().adm_sched_threshold_guided(N.ptr(x), N.ptr(eps), N.ptr(uncond), float(guidance_scale), N.ptr(coef_table),
+                                                   N.ptr(step_dev), int(step), lo, hi, w, float(max_value), N.ptr(out), B, Cc, H, W,
+                                                   N.stream_for(x), int(prediction)))
+        return out
     if prediction != 0:
         N.check(N.lib().adm_sched_threshold_pred(N.ptr(x), N.ptr(eps), N.ptr(coef_table), N.ptr(step_dev), int(step), lo, hi, w,
                                                  float(max_value), N.ptr(out), B, Cc, H, W, N.stream_for(x), int(prediction)))
@@ -53,16 +71,28 @@ def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, o
 
 
 def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
-               step_dev=None, scale_out=None, prediction=0):
+               step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None):
     """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194). x,eps: (B,C,H,W). threshold: None, or
     (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it instead of the static
     clamp (`adm_sched_step_thresholded`; scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device
     scalar that replaces `step`. prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model
-    (`adm_sched_step_pred`; include/adm.h has the table)."""
+    (`adm_sched_step_pred`; include/adm.h has the table). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional
+    model output and the step uses o = uncond + guidance_scale * (eps - uncond), combined inside the kernel (`adm_sched_step_guided`)."""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
     out = torch.empty_like(x) if out is None else out
     n_mask = mask.shape[1] if mask is not None else 0
+    if _guidance(eps, uncond, guidance_scale):
+        lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
+        if threshold is not None:
+            lo, hi, w = threshold_ranks(Cc * H * W, threshold[0])
+            max_value = threshold[1]
+            scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+        N.check(N.lib().adm_sched_step_guided(N.ptr(x), N.ptr(eps), N.ptr(uncond), float(guidance_scale), N.ptr(noise), N.ptr(out),
+                                              N.ptr(u8_out), N.ptr(coef_table), None, None, N.ptr(step_dev), int(step), N.ptr(mask),
+                                              n_mask, int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x), lo, hi, w,
+                                              float(max_value), N.ptr(scale), int(prediction)))
+        return out
     if prediction != 0:
         lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
         if threshold is not None:
@@ -89,15 +119,22 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
 
 
 def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
-                    u8_out=None, step_dev=None):
+                    u8_out=None, step_dev=None, uncond=None, guidance_scale=None):
     """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,) fp32
     beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev: optional
-    int32 device scalar that replaces `step`."""
+    int32 device scalar that replaces `step`. uncond, guidance_scale: classifier-free guidance as in sched_step; hist then holds x0 of the
+    guided output."""
     _f32(x), _f32(eps), _f32(hist), _f32(k_hist_table)
     assert hist.shape == x.shape and k_hist_table.numel() == coef_table.shape[0]
     B, Cc, H, W = x.shape
     out = torch.empty_like(x) if out is None else out
     n_mask = mask.shape[1] if mask is not None else 0
+    if _guidance(eps, uncond, guidance_scale):
+        N.check(N.lib().adm_sched_step_guided(N.ptr(x), N.ptr(eps), N.ptr(uncond), float(guidance_scale), N.ptr(noise), N.ptr(out),
+                                              N.ptr(u8_out), N.ptr(coef_table), N.ptr(k_hist_table), N.ptr(hist), N.ptr(step_dev),
+                                              int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
+                                              N.stream_for(x), 0, 0, 0.0, 1.0, None, 0))
+        return out
     N.check(N.lib().adm_sched_multistep(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
                                         N.ptr(k_hist_table), N.ptr(hist), N.ptr(step_dev), int(step), N.ptr(mask), n_mask,
                                         int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x)))

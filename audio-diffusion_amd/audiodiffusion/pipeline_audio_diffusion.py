@@ -151,11 +151,53 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         return 50 if isinstance(self.scheduler, DDIMScheduler) else 1000
 
     # ---- the native denoising loop (pipeline_audio_diffusion.py:159-185 + :192-194) ----------------------
+    def _guided(self, guidance_scale, negative_encoding, encoding):
+        """The rules of classifier-free guidance (`__call__`): True when the guided loop is to run."""
+        if guidance_scale is not None and not np.isfinite(float(guidance_scale)):   # (before the rule below: nan > 1 is False)
+            raise ValueError(f"guidance_scale={guidance_scale!r} must be finite")
+        on = guidance_scale is not None and float(guidance_scale) > 1.0   # diffusers' rule: <= 1 is today's path, exactly
+        if not on:
+            if negative_encoding is not None:
+                raise ValueError("negative_encoding is only used by classifier-free guidance: pass guidance_scale > 1 with it")
+            return False
+        if not isinstance(self.unet, UNet2DConditionModel):
+            raise ValueError("guidance_scale > 1 needs a conditional model: this pipeline's unet is not a UNet2DConditionModel")
+        if encoding is None:
+            raise ValueError("guidance_scale > 1 needs an `encoding` to guide towards: none was given")
+        return True
+
+    @staticmethod
+    def _negative_encoding(negative_encoding, enc, keep=None):
+        """The unconditional branch's encoding, of the shape of `enc` (B, seq, dim): zeros by default, a leading 1 broadcasts.
+        keep: the buffer this method made for an earlier guided call (never a caller's tensor). Its address is part of the captured graph's key, so where a new tensor would have
+        to be made (zeros, a broadcast, a conversion) `keep` is refilled in place when shape and device still fit: consecutive calls
+        then replay the captured graph instead of capturing again. A caller's own contiguous fp32 tensor is used as it is.
+        -> (the encoding to use, the buffer to keep for the next call)"""
+        fits = keep is not None and keep.shape == enc.shape and keep.device == enc.device and keep.dtype == torch.float32
+        if negative_encoding is None:
+            buf = keep.zero_() if fits else torch.zeros_like(enc)
+            return buf, buf
+        neg = negative_encoding.to(enc.device, torch.float32)
+        if neg.dim() == 2:
+            neg = neg[:, None, :]
+        if neg.dim() == 3 and neg.shape[0] == 1 and tuple(neg.shape[1:]) == tuple(enc.shape[1:]):
+            neg = neg.expand(enc.shape[0], -1, -1)
+        if tuple(neg.shape) != tuple(enc.shape):
+            raise ValueError(f"negative_encoding shape {tuple(negative_encoding.shape)} does not match the encoding's {tuple(enc.shape)} "
+                             f"(a leading 1 is broadcast over the batch)")
+        if neg is negative_encoding and neg.is_contiguous():
+            return neg, keep
+        buf = keep.copy_(neg) if fits else neg.contiguous().clone()
+        return buf, buf
+
     def _denoise(self, images, start_step, eta, step_generator, mask, mask_start, mask_end, step_noise=None,
-                 use_graph=True, want_u8=True, encoding=None, stop_step=None):
+                 use_graph=True, want_u8=True, encoding=None, stop_step=None, guidance_scale=None, negative_encoding=None):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
-        before that step index, so that a single step of a long schedule can be compared in isolation."""
+        before that step index, so that a single step of a long schedule can be compared in isolation.
+        guidance_scale > 1: every step is two forwards (the encoding, the negative encoding) and one guided step kernel, inside the
+        same native call (`adm_sample_loop_guided`); otherwise today's entry points, one forward per step."""
         sched, unet = self.scheduler, self.unet
+        guided = self._guided(guidance_scale, negative_encoding, encoding)
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
         thresh = None if multistep else sched.threshold()
         pred = 0 if multistep else sched.prediction   # 0 epsilon: today's three entry points; otherwise adm_sample_loop_pred
@@ -169,6 +211,10 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         h = unet._ensure_handle()
         if isinstance(unet, UNet2DConditionModel):     # `self.unet(images, t, encoding)` (:160-161): constant over the loop
             unet._set_encoding(h, encoding, B, x.device)
+        if guided:
+            # kept alive, and reused by the next call: the captured graph holds the pointer
+            unet._enc_uncond, unet._enc_uncond_buf = self._negative_encoding(negative_encoding, unet._enc,
+                                                                             getattr(unet, "_enc_uncond_buf", None))
         u8 = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=x.device) if want_u8 else None
         if Cc != 1 and want_u8:
             u8 = None  # NHWC permute for multi-channel images is done after the loop
@@ -200,7 +246,15 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 mask_chunk = mask[:, done:done + m].contiguous()
                 mask_ptr = N.ptr(mask_chunk)
             u8_ptr = N.ptr(u8) if (last and u8 is not None) else None
-            if multistep:   # no noise, so no chunking: the history of the previous x0 lives inside this one native call
+            if guided:   # every mode through the one guided entry point; the multistep loop stays one call
+                assert not multistep or m == n
+                khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub]) if multistep else None
+                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
+                N.check(N.lib().adm_sample_loop_guided(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
+                                                       int(mask_end), u8_ptr, int(use_graph), N.stream_for(x), lo, hi, w,
+                                                       thresh[1] if thresh is not None else 1.0, int(thresh is not None), pred,
+                                                       N.ptr(unet._enc_uncond), float(guidance_scale)))
+            elif multistep:   # no noise, so no chunking: the history of the previous x0 lives inside this one native call
                 assert m == n
                 khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
                 N.check(N.lib().adm_sample_loop_multistep(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
@@ -244,13 +298,25 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         audio=True,
         return_float=False,
         init_phase=None,
+        guidance_scale=None,
+        negative_encoding=None,
     ) -> Union[PipelineOutput, Tuple[List[Image.Image], Tuple[int, List[np.ndarray]]]]:
         """Generate random mel spectrogram from audio input and convert to audio (reference docstring `:89-112`).
 
         Extra keyword-only knobs (not in the reference; defaults reproduce it): `step_noise` injects the
         per-step scheduler noise (parity tests), `audio=False` skips the image->audio conversion,
         `return_float=True` additionally returns the final float images, `init_phase` (B, n_bins, frames) replaces the
-        unseeded Griffin-Lim start phase librosa draws (`mel.py:165-167`)."""
+        unseeded Griffin-Lim start phase librosa draws (`mel.py:165-167`).
+
+        Classifier-free guidance (Ho & Salimans 2022), off by default: `guidance_scale` g and `negative_encoding`.
+          * g None or <= 1.0 takes the unguided path exactly: one forward per step and the unguided entry points (diffusers' rule;
+            u + 1*(c - u) is not c in floating point, so 1.0 never goes through the guided kernel).
+          * g > 1 needs a UNet2DConditionModel and an `encoding`; otherwise ValueError naming what is missing. Every step then runs the
+            model on the encoding (c) and on the negative encoding (u) and steps with u + g*(c - u), all inside the captured loop.
+          * `negative_encoding` None means zeros of the encoding's shape (what `train_unet.py --encoding_dropout` trains the model
+            to read as "no condition"); otherwise it must have the encoding's shape, a leading 1 being broadcast over the batch.
+          * a `negative_encoding` without g > 1 is a ValueError."""
+        self._guided(guidance_scale, negative_encoding, encoding)   # the ValueErrors, before any work
         steps = steps or self.get_default_steps()
         self.scheduler.set_timesteps(steps)
         step_generator = step_generator or generator
@@ -294,7 +360,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
 
         use_mask = mask if (mask is not None and (mask_start > 0 or mask_end > 0)) else None
         images, u8 = self._denoise(images, start_step, eta, step_generator, use_mask, mask_start, mask_end,
-                                   step_noise=step_noise, want_u8=self.vqvae is None, encoding=encoding)
+                                   step_noise=step_noise, want_u8=self.vqvae is None, encoding=encoding,
+                                   guidance_scale=guidance_scale, negative_encoding=negative_encoding)
 
         if self.vqvae is not None:
             # 0.18215 was scaling factor used in training to ensure unit variance (pipeline:187-190); the 1/0.18215

@@ -16,6 +16,9 @@ of the noise. The coefficient rows do not change; the step and selection kernels
 `ops.noise_and_velocity` give the training target. With them come `timestep_spacing` "linspace" / "trailing" and
 `rescale_betas_zero_snr` (Lin et al. 2023), whose last training timestep has alphas_cumprod == 0: only the two new types can start
 there, an epsilon scheduler refuses such a schedule. The multistep scheduler stays epsilon-only.
+Classifier-free guidance: `step(..., model_output_uncond=u, guidance_scale=g)` of the three schedulers takes the conditional output as
+`model_output` and steps with u + g*(model_output - u), combined inside the one fused kernel (`adm_sched_step_guided`; the
+thresholded and the multistep paths included). Both keywords or neither; the `<= 1 means off` rule belongs to the pipeline.
 """
 import json
 import math
@@ -244,7 +247,7 @@ class _SchedulerBase:
             return None
         return float(self.config.dynamic_thresholding_ratio), float(self.config.sample_max_value)
 
-    def _step(self, model_output, timestep, sample, eta, generator, variance_noise):
+    def _step(self, model_output, timestep, sample, eta, generator, variance_noise, model_output_uncond=None, guidance_scale=None):
         i = self._index_of(timestep)
         _, table, rows = self._cached(sample.device, eta)
         need_noise = rows[i]["k_noise"] != 0.0
@@ -252,7 +255,9 @@ class _SchedulerBase:
             variance_noise = randn_tensor(model_output.shape, generator, model_output.device, model_output.dtype)
         prev = ops.sched_step(sample.contiguous(), model_output.contiguous(), table, i,
                               noise=variance_noise.contiguous() if variance_noise is not None else None,
-                              threshold=self.threshold(), prediction=self.prediction)
+                              threshold=self.threshold(), prediction=self.prediction,
+                              uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
+                              guidance_scale=guidance_scale)
         return SchedulerOutput(prev_sample=prev)
 
 
@@ -287,8 +292,9 @@ class DDPMScheduler(_SchedulerBase):
                              k_eps=0.0, k_noise=k_noise, timestep=float(t)))
         return rows
 
-    def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None):
-        return self._step(model_output, timestep, sample, 0.0, generator, variance_noise)
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None, *,
+             model_output_uncond=None, guidance_scale=None):
+        return self._step(model_output, timestep, sample, 0.0, generator, variance_noise, model_output_uncond, guidance_scale)
 
 
 class DDIMScheduler(_SchedulerBase):
@@ -333,10 +339,10 @@ class DDIMScheduler(_SchedulerBase):
         return rows
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
-             variance_noise=None, return_dict=True):
+             variance_noise=None, return_dict=True, *, model_output_uncond=None, guidance_scale=None):
         if use_clipped_model_output:
             raise NotImplementedError("use_clipped_model_output is not implemented (the reference never sets it)")
-        return self._step(model_output, timestep, sample, float(eta), generator, variance_noise)
+        return self._step(model_output, timestep, sample, float(eta), generator, variance_noise, model_output_uncond, guidance_scale)
 
 
 def _f32(v):
@@ -489,8 +495,9 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         return self._run_rows(0)
 
     # ---- eager step ---------------------------------------------------------------------------------------
-    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True):
-        """One fused kernel. First order on the first call after `set_timesteps` (and whenever the call does not continue the
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, *,
+             model_output_uncond=None, guidance_scale=None):
+        """One fused kernel (with model_output_uncond and guidance_scale: the guided one, whose history is x0 of the guided output). First order on the first call after `set_timesteps` (and whenever the call does not continue the
         previous one: another row than the next, another shape or device); the scheduler holds the history tensor."""
         i = self._index_of(timestep)
         fresh = (self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device)
@@ -504,7 +511,9 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             self._ms_tables = {key: (ops.sched_coef_table(rows, sample.device),
                                      torch.tensor([r["k_hist"] for r in rows], dtype=torch.float32).to(sample.device))}
         table, khist = self._ms_tables[key]
-        prev = ops.sched_multistep(sample.contiguous(), model_output.contiguous(), table, khist, self._hist, i)
+        prev = ops.sched_multistep(sample.contiguous(), model_output.contiguous(), table, khist, self._hist, i,
+                                   uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
+                                   guidance_scale=guidance_scale)
         self._last_index = i
         if not return_dict:
             return (prev,)

@@ -14,13 +14,14 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
   long noise_step_stride = 0; int u8_step = -1;           // captured loop: per-step noise slice; the one step that writes u8 (-1: every)
   int lo = 0, hi = 0; float w = 0.f, max_value = 1.f; float* scale = nullptr;   // SCHED_THRESH: ranks, weight, maximum; (B,) thresholds
   float* hist = nullptr; const float* k_hist_table = nullptr;                   // SCHED_MULTISTEP
+  const float* eps_uncond = nullptr; float guidance = 1.f;   // classifier-free guidance: eps is the conditional output, o = u + g*(c - u)
   long per_sample = 0, n4 = 0, mask_bstride = 0;          // derived from the shape by launch_sched_step
 };
 int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
 int launch_step_advance(int* step_dev, hipStream_t st);
 int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
                            int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st,
-                           int pred = PRED_EPSILON);
+                           int pred = PRED_EPSILON, const float* eps_uncond = nullptr, float guidance = 1.f);
 int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

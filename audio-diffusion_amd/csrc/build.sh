@@ -13,12 +13,14 @@ cd "$here"
 exp=""; suf=""
 if [ "${1:-hip}" = "emu" ]; then
   out="$root/tests/emu/libadm_emu$suf.so"
+  # -ffp-contract=off: the emulator never fuses a product and a sum on its own (fmaf() written out still does), whatever the host's
+  # -march; kernels that promise separately rounded operations (sched_guided) are then checked against that promise
   objs=()
   mkdir -p "$root/tests/emu/obj$suf"
   for s in "${srcs[@]}"; do
     o="$root/tests/emu/obj$suf/${s%.hip}.o"
     if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ adm_rt.h -nt "$o" ] || [ adm_kernels.h -nt "$o" ] || [ net_exec.h -nt "$o" ] || [ k_conv_wino.h -nt "$o" ] || [ "$root/tests/emu/hip_emu.h" -nt "$o" ] || [ "$root/include/adm.h" -nt "$o" ]; then
-      g++ -O2 -g -std=c++17 -fPIC -DADM_EMU $exp -I"$root/tests/emu" -x c++ -c "$s" -o "$o" -Wall -Wno-unknown-pragmas -Wno-unused-variable -Wno-unused-function -Wno-sign-compare -Wno-psabi &
+      g++ -O2 -g -std=c++17 -fPIC -ffp-contract=off -DADM_EMU $exp -I"$root/tests/emu" -x c++ -c "$s" -o "$o" -Wall -Wno-unknown-pragmas -Wno-unused-variable -Wno-unused-function -Wno-sign-compare -Wno-psabi &
     fi
     objs+=("$o")
   done

@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 111; }   // 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 112; }   // 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -149,6 +149,32 @@ int adm_sched_step_pred(const float* x, const float* eps, const float* noise, fl
                         float max_value, float* scale, int prediction) {
   ADM_REQUIRE(x && eps && out && coef_table, "sched_step_pred: null argument");
   SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
+  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
+  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);
+}
+
+int adm_sched_threshold_guided(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale,
+                               const adm_sched_coef* coef_table, const int* step_dev, int step, int lo, int hi, float w, float max_value,
+                               float* scale_out, int B, int C, int H, int W, void* stream, int prediction) {
+  ADM_REQUIRE(x && eps_cond && eps_uncond && coef_table && scale_out, "sched_threshold_guided: null argument");
+  return launch_sched_threshold(x, eps_cond, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W,
+                                (hipStream_t)stream, prediction, eps_uncond, guidance_scale);
+}
+
+int adm_sched_step_guided(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale, const float* noise,
+                          float* out, uint8_t* u8_out, const adm_sched_coef* coef_table, const float* k_hist_table, float* hist,
+                          const int* step_dev, int step, const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C,
+                          int H, int W, void* stream, int lo, int hi, float w, float max_value, float* scale, int prediction) {
+  ADM_REQUIRE(x && eps_cond && eps_uncond && out && coef_table, "sched_step_guided: null argument");
+  SchedStepParams p{x, eps_cond, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  p.eps_uncond = eps_uncond; p.guidance = guidance_scale;
+  if (hist != nullptr) {
+    ADM_REQUIRE(k_hist_table != nullptr, "sched_step_guided: the multistep step needs k_hist_table");
+    ADM_REQUIRE(prediction == PRED_EPSILON && scale == nullptr, "sched_step_guided: the multistep step is epsilon only and not thresholded");
+    p.hist = hist; p.k_hist_table = k_hist_table;
+    return launch_sched_step(p, SCHED_MULTISTEP, (hipStream_t)stream);
+  }
   if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
   p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
   return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);

@@ -17,7 +17,13 @@
 // key: sched_step_kernel<MODE> and sched_threshold_kernel are the epsilon instantiations under their old names, sched_step_pred_kernel
 // <MODE, PRED> and sched_threshold_pred_kernel<PRED> the sample / v_prediction ones (SCHED_PLAIN and SCHED_THRESH; the multistep step is
 // epsilon only). Same traffic: the parameterisation only changes the few flops that turn (x, model output) into (x0, eps).
+// Classifier-free guidance (GUIDED, the third template parameter of the same body and of the selection's key): p.eps is the conditional
+// model output c, p.eps_uncond the unconditional one u, and o = sched_guided(u, c, g) stands wherever the model output stood. One more
+// float4 load per lane: 16 B/elem where the unguided step moves 12 (+4 with noise, +8 with the multistep history, as before); every pass of
+// the selection reads 12 B/elem instead of 8. sched_step_guided_kernel<MODE, PRED> / sched_threshold_guided_kernel<PRED>: plain and
+// thresholded for the three prediction types, multistep for epsilon. The unguided kernels keep their names and their arithmetic.
 #include "adm_kernels.h"
+#include <cmath>
 
 namespace adm {
 
@@ -43,6 +49,17 @@ __device__ __forceinline__ float sched_eps(float x, float o, float x0, const adm
   return o;
 }
 
+// classifier-free guidance: diffusers' `uncond + scale * (cond - uncond)` with its three separate roundings. ONE helper for the step
+// body and the selection's key, so that both see the same bits. Plain operators under `fp contract(off)`, not __fadd_rn / __fmul_rn: hipcc's
+// headers define those as `x + y` / `x * y` compiled under the default contraction, and once inlined the product and the sum fuse into
+// fma(g, c - u, u), one rounding fewer than torch's. u == c gives u at any finite g.
+__device__ __forceinline__ float sched_guided(float u, float c, float g) {
+#pragma clang fp contract(off)
+  const float d = c - u;
+  const float gd = g * d;
+  return u + gd;
+}
+
 __device__ __forceinline__ unsigned char quant_u8(float v) {
   float q = fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f) * 255.f;
   return (unsigned char)rintf(q);  // round-half-even == numpy .round() (pipeline:194)
@@ -61,10 +78,11 @@ __device__ __forceinline__ unsigned pack_u8x4(float a, float b, float c, float d
 //                    hist is read ONLY where k_hist != 0: the first row of a run has k_hist == 0 and finds the buffer uninitialised
 //                    (0 * NaN must not reach the output). Each lane reads and rewrites its own elements of hist.
 // PRED: what p.eps holds (the model output o); e below is sched_eps of it, the model output itself for PRED_EPSILON.
+// GUIDED: p.eps is the conditional output and o = sched_guided(p.eps_uncond, p.eps, p.guidance): in x0, in e and so in the history m0.
 // out may alias x.
 // first, stride: the lane's first float4 and the grid's stride, which the kernel works out itself (a launch-geometry builtin is only
 // folded against the kernel's launch bounds where the kernel reads it).
-template <int MODE, int PRED>
+template <int MODE, int PRED, bool GUIDED>
 __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const long first, const long stride) {
   const int s = p.step_dev ? *p.step_dev : p.step;
   const adm_sched_coef c = p.table[s];
@@ -75,7 +93,12 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
   unsigned char* u8 = p.u8_step >= 0 && s != p.u8_step ? nullptr : p.u8;
   for (long i = first; i < p.n4; i += stride) {
     const float4 xv = reinterpret_cast<const float4*>(p.x)[i];
-    const float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
+    float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
+    if (GUIDED) {
+      const float4 uv = reinterpret_cast<const float4*>(p.eps_uncond)[i];
+      ev = make_float4(sched_guided(uv.x, ev.x, p.guidance), sched_guided(uv.y, ev.y, p.guidance), sched_guided(uv.z, ev.z, p.guidance),
+                       sched_guided(uv.w, ev.w, p.guidance));
+    }
     float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
     if (use_hist) hv = reinterpret_cast<const float4*>(p.hist)[i];
@@ -120,13 +143,19 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
 
 template <int MODE>
 __global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p) {
-  sched_step_body<MODE, PRED_EPSILON>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+  sched_step_body<MODE, PRED_EPSILON, false>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 template <int MODE, int PRED>
 __global__ void __launch_bounds__(256) sched_step_pred_kernel(const SchedStepParams p) {
   static_assert(MODE != SCHED_MULTISTEP && PRED != PRED_EPSILON, "the sample / v_prediction steps: plain and thresholded only");
-  sched_step_body<MODE, PRED>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+  sched_step_body<MODE, PRED, false>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+template <int MODE, int PRED>
+__global__ void __launch_bounds__(256) sched_step_guided_kernel(const SchedStepParams p) {
+  static_assert(MODE != SCHED_MULTISTEP || PRED == PRED_EPSILON, "the multistep step is epsilon only");
+  sched_step_body<MODE, PRED, true>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 // ---- dynamic threshold: exact per-sample order statistics of |x0| ---------------------------------------------------------------------
@@ -148,21 +177,28 @@ __device__ __forceinline__ float thresh_bits_to_float(unsigned u) {
   return f;
 }
 
-// One sweep of a sample: f(key) for the key of every element. Four float4 pairs per lane are loaded before any is used: with one workgroup
-// per sample (a single CU when B = 1) the sweep is bound by load latency, not by bandwidth.
-template <int PRED, class F>
-__device__ __forceinline__ void thresh_sweep(const float4* __restrict__ xp, const float4* __restrict__ ep, int n4, int tid,
-                                             const adm_sched_coef& c, F f) {
+// One sweep of a sample: f(key) for the key of every element. Four float4 pairs (GUIDED: triples) per lane are loaded before any is used:
+// with one workgroup per sample (a single CU when B = 1) the sweep is bound by load latency, not by bandwidth.
+// GUIDED: up is the unconditional output and the key is |x0| of sched_guided(up, ep, g), the step body's own combination.
+template <int PRED, bool GUIDED, class F>
+__device__ __forceinline__ void thresh_sweep(const float4* __restrict__ xp, const float4* __restrict__ ep, const float4* __restrict__ up,
+                                             float g, int n4, int tid, const adm_sched_coef& c, F f) {
   for (int i0 = tid; i0 < n4; i0 += 4 * kThreshThreads) {
-    float4 xv[4], ev[4];
+    float4 xv[4], ev[4], uv[4];
     ADM_UNROLL
     for (int u = 0; u < 4; ++u) {
       const int i = i0 + u * kThreshThreads;
-      if (i < n4) { xv[u] = xp[i]; ev[u] = ep[i]; }
+      if (i < n4) {
+        xv[u] = xp[i]; ev[u] = ep[i];
+        if (GUIDED) uv[u] = up[i];
+      }
     }
     ADM_UNROLL
     for (int u = 0; u < 4; ++u) {
       if (i0 + u * kThreshThreads < n4) {
+        if (GUIDED)
+          ev[u] = make_float4(sched_guided(uv[u].x, ev[u].x, g), sched_guided(uv[u].y, ev[u].y, g), sched_guided(uv[u].z, ev[u].z, g),
+                              sched_guided(uv[u].w, ev[u].w, g));
         f(thresh_key<PRED>(xv[u].x, ev[u].x, c)); f(thresh_key<PRED>(xv[u].y, ev[u].y, c));
         f(thresh_key<PRED>(xv[u].z, ev[u].z, c)); f(thresh_key<PRED>(xv[u].w, ev[u].w, c));
       }
@@ -191,9 +227,10 @@ __device__ __forceinline__ void thresh_find_bin(const unsigned* hist, int nbins,
   }
 }
 
-template <int PRED>
+template <int PRED, bool GUIDED>
 __device__ __forceinline__ void sched_threshold_body(
-    const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
+    const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_uncond, float guidance,
+    const adm_sched_coef* __restrict__ table,
     const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
     float* __restrict__ scale) {
   __shared__ unsigned hist[kThreshBins];
@@ -201,6 +238,7 @@ __device__ __forceinline__ void sched_threshold_body(
   const adm_sched_coef c = table[step_dev ? *step_dev : step];
   const float4* xp = reinterpret_cast<const float4*>(x + (long)blockIdx.x * per_sample);
   const float4* ep = reinterpret_cast<const float4*>(eps + (long)blockIdx.x * per_sample);
+  const float4* uq = GUIDED ? reinterpret_cast<const float4*>(eps_uncond + (long)blockIdx.x * per_sample) : nullptr;
   const int n4 = (int)(per_sample >> 2);
   const int tid = threadIdx.x;
   if (tid < 3) sel[tid] = 0;
@@ -211,7 +249,7 @@ __device__ __forceinline__ void sched_threshold_body(
     const int up = pass == 0 ? 31 : shift + 10;                // the digits above this one are fixed by `prefix`
     for (int j = tid; j < nbins; j += kThreshThreads) hist[j] = 0;
     __syncthreads();
-    thresh_sweep<PRED>(xp, ep, n4, tid, c, [&](unsigned key) {
+    thresh_sweep<PRED, GUIDED>(xp, ep, uq, guidance, n4, tid, c, [&](unsigned key) {
       if ((key >> up) == (prefix >> up)) atomicAdd(&hist[(key >> shift) & (unsigned)(nbins - 1)], 1u);
     });
     __syncthreads();
@@ -227,7 +265,7 @@ __device__ __forceinline__ void sched_threshold_body(
     if (tid == 0) hist[0] = 0;
     __syncthreads();
     unsigned m = 0xffffffffu;
-    thresh_sweep<PRED>(xp, ep, n4, tid, c, [&](unsigned key) {
+    thresh_sweep<PRED, GUIDED>(xp, ep, uq, guidance, n4, tid, c, [&](unsigned key) {
       if (key > prefix && key < m) m = key;
     });
     for (int d = 32; d >= 1; d >>= 1) {
@@ -253,7 +291,7 @@ __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
     const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
     const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
     float* __restrict__ scale) {
-  sched_threshold_body<PRED_EPSILON>(x, eps, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
+  sched_threshold_body<PRED_EPSILON, false>(x, eps, nullptr, 1.f, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
 }
 
 template <int PRED>
@@ -261,7 +299,15 @@ __global__ void __launch_bounds__(kThreshThreads) sched_threshold_pred_kernel(
     const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
     const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
     float* __restrict__ scale) {
-  sched_threshold_body<PRED>(x, eps, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
+  sched_threshold_body<PRED, false>(x, eps, nullptr, 1.f, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
+}
+
+template <int PRED>
+__global__ void __launch_bounds__(kThreshThreads) sched_threshold_guided_kernel(
+    const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_uncond, float guidance,
+    const adm_sched_coef* __restrict__ table, const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w,
+    float max_value, float* __restrict__ scale) {
+  sched_threshold_body<PRED, true>(x, eps, eps_uncond, guidance, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
 }
 
 __global__ void step_advance_kernel(int* step_dev) { *step_dev += 1; }
@@ -336,7 +382,8 @@ static inline int ew_grid(long n4) {
 }
 
 int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
-                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st, int pred) {
+                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st, int pred,
+                           const float* eps_uncond, float guidance) {
   const long per_sample = (long)C * H * W;
   ADM_REQUIRE(B > 0 && W % 4 == 0, "sched_threshold: W must be a multiple of 4");
   ADM_REQUIRE(per_sample > 0 && per_sample < (1L << 31), "sched_threshold: C*H*W must be below 2^31");
@@ -345,6 +392,19 @@ int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coe
   ADM_REQUIRE(max_value >= 1.f, "sched_threshold: max_value must be >= 1");
   ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_threshold: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
   const dim3 grid(B), block(kThreshThreads);
+  if (eps_uncond != nullptr) {
+    ADM_REQUIRE(std::isfinite(guidance), "sched_threshold: the guidance scale must be finite");
+    if (pred == PRED_SAMPLE)
+      ADM_LAUNCH(sched_threshold_guided_kernel<PRED_SAMPLE>, grid, block, 0, st, x, eps, eps_uncond, guidance, table, step_dev, step,
+                 per_sample, (unsigned)lo, (unsigned)hi, w, max_value, scale);
+    else if (pred == PRED_V)
+      ADM_LAUNCH(sched_threshold_guided_kernel<PRED_V>, grid, block, 0, st, x, eps, eps_uncond, guidance, table, step_dev, step,
+                 per_sample, (unsigned)lo, (unsigned)hi, w, max_value, scale);
+    else
+      ADM_LAUNCH(sched_threshold_guided_kernel<PRED_EPSILON>, grid, block, 0, st, x, eps, eps_uncond, guidance, table, step_dev, step,
+                 per_sample, (unsigned)lo, (unsigned)hi, w, max_value, scale);
+    return ADM_CHECK_LAUNCH();
+  }
   if (pred == PRED_SAMPLE)
     ADM_LAUNCH(sched_threshold_pred_kernel<PRED_SAMPLE>, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo,
                (unsigned)hi, w, max_value, scale);
@@ -366,22 +426,35 @@ int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int p
   p.n4 = p.per_sample * p.B / 4;
   p.mask_bstride = (long)p.n_mask_steps * p.per_sample;
   const dim3 grid(ew_grid(p.n4)), block(256);
+  const bool guided = p.eps_uncond != nullptr;
+  if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_step: the guidance scale must be finite");
   if (mode == SCHED_THRESH) {
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_thresholded: mask path requires C == 1 (as in the reference)");
     ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,
-                                   p.W, st, pred));
-    if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_SAMPLE>), grid, block, 0, st, p);
+                                   p.W, st, pred, p.eps_uncond, p.guidance));
+    if (guided) {
+      if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_guided_kernel<SCHED_THRESH, PRED_SAMPLE>), grid, block, 0, st, p);
+      else if (pred == PRED_V) ADM_LAUNCH((sched_step_guided_kernel<SCHED_THRESH, PRED_V>), grid, block, 0, st, p);
+      else ADM_LAUNCH((sched_step_guided_kernel<SCHED_THRESH, PRED_EPSILON>), grid, block, 0, st, p);
+    }
+    else if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_SAMPLE>), grid, block, 0, st, p);
     else if (pred == PRED_V) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_V>), grid, block, 0, st, p);
     else ADM_LAUNCH(sched_step_kernel<SCHED_THRESH>, grid, block, 0, st, p);
   } else if (mode == SCHED_MULTISTEP) {
     ADM_REQUIRE(p.W % 4 == 0, "sched_multistep: W must be a multiple of 4");
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_multistep: mask path requires C == 1 (as in the reference)");
-    ADM_LAUNCH(sched_step_kernel<SCHED_MULTISTEP>, grid, block, 0, st, p);
+    if (guided) ADM_LAUNCH((sched_step_guided_kernel<SCHED_MULTISTEP, PRED_EPSILON>), grid, block, 0, st, p);
+    else ADM_LAUNCH(sched_step_kernel<SCHED_MULTISTEP>, grid, block, 0, st, p);
   } else {
     ADM_REQUIRE(mode == SCHED_PLAIN, "sched_step: unknown mode");
     ADM_REQUIRE(p.W % 4 == 0, "sched_step: W must be a multiple of 4");
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
-    if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_SAMPLE>), grid, block, 0, st, p);
+    if (guided) {
+      if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_guided_kernel<SCHED_PLAIN, PRED_SAMPLE>), grid, block, 0, st, p);
+      else if (pred == PRED_V) ADM_LAUNCH((sched_step_guided_kernel<SCHED_PLAIN, PRED_V>), grid, block, 0, st, p);
+      else ADM_LAUNCH((sched_step_guided_kernel<SCHED_PLAIN, PRED_EPSILON>), grid, block, 0, st, p);
+    }
+    else if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_SAMPLE>), grid, block, 0, st, p);
     else if (pred == PRED_V) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_V>), grid, block, 0, st, p);
     else ADM_LAUNCH(sched_step_kernel<SCHED_PLAIN>, grid, block, 0, st, p);
   }

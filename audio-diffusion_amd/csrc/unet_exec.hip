@@ -38,6 +38,8 @@ struct adm_unet {
   float *emb = nullptr, *emb_act = nullptr, *temb_all = nullptr, *t_dev = nullptr, *eps_buf = nullptr;
   float* hist_buf = nullptr;     // x0 of the previous step (multistep scheduler loop); same size as eps_buf
   float* scale_buf = nullptr;    // per-sample dynamic threshold of the thresholded loop (B floats)
+  float* eps_uncond_buf = nullptr;   // the unconditional forward's output of a guided loop; same size as eps_buf, allocated with the
+                                     // plan by the first guided loop at this batch size (free_plan releases it with the other extras)
   adm_sched_coef* coef_dev = nullptr;
   int coef_cap = 0;
   float* khist_dev = nullptr;    // per-step history coefficient of the multistep loop, beside coef_dev
@@ -257,6 +259,7 @@ static void free_plan(adm_unet* h) {
   for (void* p : h->extra) dfree(p);
   h->extra.clear();
   h->planned_B = 0;
+  h->eps_uncond_buf = nullptr;
   h->warm_B = 0;       // the next capture is preceded by an uncaptured forward again (another kernel's one-time set-up)
 #if !defined(ADM_EMU)
   if (h->gexec) {                     // (a replay may still be in flight: drain the stream it ran on before the executable graph goes)
@@ -343,6 +346,8 @@ struct LoopArgs {
   uint8_t* u8; int mode; const float* k_hist_host;
   int th_lo = 0, th_hi = 0; float th_w = 0.f, th_max = 1.f;   // SCHED_THRESH: the two ranks, their weight and sample_max_value
   int pred = PRED_EPSILON;                                    // what the model output is: chooses the step (and selection) kernel
+  // classifier-free guidance (both set, or neither): the unconditional encoding, device, of the shape of the handle's encoding, and the scale
+  const float* ctx_uncond = nullptr; float guidance = 1.f;
 };
 
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
@@ -350,6 +355,16 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
   const adm_unet_config& c = h->cfg;
   const adm_sched_coef* table = h->coef_dev;
   ADM_TRY(run_forward(h, a.x, h->eps_buf, a.B, table, st));
+  if (a.ctx_uncond != nullptr) {
+    // The unconditional branch: a second forward of batch B on the SAME plan (its side-stream hoists included), with the encoding pointer
+    // swapped. Nothing derived from the encoding outlives a forward (the cross-attention kernel projects K and V from net.ctx inside every
+    // launch), so the swap is all it takes; both forwards run in stream order, the second after the first has joined its side launches.
+    const float* ctx_cond = h->net.ctx;
+    h->net.ctx = a.ctx_uncond;
+    const int rc = run_forward(h, a.x, h->eps_uncond_buf, a.B, table, st);
+    h->net.ctx = ctx_cond;
+    ADM_TRY(rc);
+  }
   const long n = (long)a.B * c.in_channels * c.sample_h * c.sample_w;
   if (a.mode == LOOP_ENCODE) {
     ADM_TRY(launch_encode_step(a.x, h->eps_buf, table, h->step_dev, step, n, st));
@@ -359,6 +374,7 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
     p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
     p.lo = a.th_lo; p.hi = a.th_hi; p.w = a.th_w; p.max_value = a.th_max; p.scale = h->scale_buf;
     p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
+    if (a.ctx_uncond != nullptr) { p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance; }
     ADM_TRY(launch_sched_step(p, a.mode, st, a.pred));
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
@@ -369,6 +385,9 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
   ADM_TRY(finalize(h));
   ADM_REQUIRE(h->cfg.in_channels == h->cfg.out_channels, "sample_loop: in/out channels differ");
   ADM_TRY(plan(h, a.B));
+  if (a.ctx_uncond != nullptr && h->eps_uncond_buf == nullptr)
+    ADM_TRY(extra_alloc(h, (void**)&h->eps_uncond_buf,
+                        sizeof(float) * (size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
 #if defined(ADM_EMU)
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
@@ -400,6 +419,11 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
       memcpy(&wb, &a.th_w, 4); memcpy(&mb, &a.th_max, 4);
       key.push_back((uint64_t)h->scale_buf); key.push_back((uint64_t)a.th_lo); key.push_back((uint64_t)a.th_hi);
       key.push_back(wb); key.push_back(mb);
+    }
+    if (a.ctx_uncond != nullptr) {  // the second forward's encoding and output, and the scale: all baked into the captured nodes
+      uint32_t gb;
+      memcpy(&gb, &a.guidance, 4);
+      key.push_back((uint64_t)a.ctx_uncond); key.push_back((uint64_t)h->eps_uncond_buf); key.push_back(0x100000000ull | gb);
     }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
@@ -709,6 +733,29 @@ int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* c
   LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, thresholded ? SCHED_THRESH : SCHED_PLAIN, nullptr};
   if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
   a.pred = prediction;
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+}
+
+int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host, int n_steps,
+                           const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out, int use_graph,
+                           void* stream, int lo, int hi, float w, float max_value, int thresholded, int prediction,
+                           const float* encoding_uncond_dev, float guidance_scale) {
+  ADM_REQUIRE(h && x && coef_host && n_steps > 0 && encoding_uncond_dev, "sample_loop_guided: bad argument");
+  ADM_REQUIRE(h->cfg.cross_attention_dim > 0, "sample_loop_guided: this model has no cross-attention (UNet2DModel): nothing to guide");
+  ADM_REQUIRE(h->net.ctx != nullptr && h->net.ctx_S > 0, "sample_loop_guided: no encoding set (adm_unet_set_encoding)");
+  ADM_REQUIRE(std::isfinite(guidance_scale), "sample_loop_guided: the guidance scale must be finite");
+  ADM_REQUIRE(prediction >= PRED_EPSILON && prediction <= PRED_V,
+              "sample_loop_guided: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  int mode = thresholded ? SCHED_THRESH : SCHED_PLAIN;
+  if (k_hist_host != nullptr) {
+    ADM_REQUIRE(!thresholded && prediction == PRED_EPSILON, "sample_loop_guided: the multistep loop is epsilon only and not thresholded");
+    ADM_REQUIRE(k_hist_host[0] == 0.f, "sample_loop_guided: the first row of a run must be first order (k_hist[0] == 0)");
+    mode = SCHED_MULTISTEP;
+  }
+  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, mode, k_hist_host};
+  if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
+  a.pred = prediction;
+  a.ctx_uncond = encoding_uncond_dev; a.guidance = guidance_scale;
   return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 

@@ -138,6 +138,10 @@ def main(args):
         dist.init_process_group("nccl" if on_gpu else "gloo")
     output_dir = os.environ.get("SM_MODEL_DIR", None) or args.output_dir
 
+    if not 0.0 <= args.encoding_dropout <= 1.0:
+        raise ValueError(f"--encoding_dropout {args.encoding_dropout} must be a probability in [0, 1]")
+    if args.encoding_dropout > 0 and args.encodings is None:
+        raise ValueError("--encoding_dropout needs --encodings: an unconditional model has no encoding to drop")
     resolution = (args.resolution, args.resolution) if isinstance(args.resolution, int) else args.resolution
     images, audio_files = load_images(args, resolution)            # (N,1,H,W) uint8
     resolution = tuple(images.shape[2:])
@@ -204,6 +208,7 @@ def main(args):
                 ema.optimization_step = global_step
             continue
         g = torch.Generator().manual_seed(args.seed + epoch)
+        g_drop = encoding_dropout_generator(args.seed, epoch, rank)
         perm = torch.randperm(len(images), generator=g)[rank::world][:n_local]   # DataLoader(shuffle=True), sharded by rank
         t0, seen = time.perf_counter(), 0
         for it in range(steps_per_epoch):
@@ -213,8 +218,10 @@ def main(args):
                 clean = vqvae.encode(clean.contiguous()).latent_dist.sample() * 0.18215
             noise = torch.randn(clean.shape).to(dev)                          # CPU RNG then H2D, as :238
             timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (clean.shape[0],)).long()
-            loss = tr.step(noise_scheduler, clean, noise, timesteps, None if enc_table is None else enc_table[idx].to(dev),
-                           last_batch=(it == steps_per_epoch - 1))
+            encoding = None
+            if enc_table is not None:
+                encoding = drop_encodings(enc_table[idx], args.encoding_dropout, g_drop).to(dev)
+            loss = tr.step(noise_scheduler, clean, noise, timesteps, encoding, last_batch=(it == steps_per_epoch - 1))
             global_step += 1
             seen += clean.shape[0] * world
             if rank == 0 and (it % args.log_every == 0 or it == steps_per_epoch - 1):
@@ -242,6 +249,27 @@ def main(args):
     return model
 
 
+def encoding_dropout_generator(seed, epoch, rank):
+    """The CPU generator of one (epoch, rank)'s conditioning-dropout draws: its own stream, so that neither the global RNG (noise,
+    timesteps) nor the epoch's permutation moves when --encoding_dropout does."""
+    return torch.Generator().manual_seed(((int(seed) * 1000003 + int(epoch)) * 1000003 + int(rank) + 0x9E3779B9) % (1 << 63))
+
+
+def encoding_drop_mask(batch, p, generator):
+    """(batch,) bool: the rows of this batch whose encoding is dropped; one uniform draw per sample, row dropped where it is < p."""
+    return torch.rand(batch, generator=generator) < float(p)
+
+
+def drop_encodings(encoding, p, generator):
+    """Conditioning dropout for classifier-free guidance (Ho & Salimans 2022): per sample, with probability p, the host (B, seq, dim)
+    encoding row is replaced by zeros, the null encoding that guided sampling uses by default. p == 0 draws nothing."""
+    if not p:
+        return encoding
+    out = encoding.clone()
+    out[encoding_drop_mask(encoding.shape[0], p, generator)] = 0.0
+    return out
+
+
 def write_samples(pipeline, args, epoch, output_dir, dev, encodings):
     """`eval_batch_size` samples from the current (EMA) weights with the reference's fixed seeds (generator 42,
     random.seed(42) for the encodings, :313-329), written as PNG + peak-normalised WAV files under
@@ -255,7 +283,8 @@ def write_samples(pipeline, args, epoch, output_dir, dev, encodings):
         encoding = torch.stack(random.sample(encodings, min(args.eval_batch_size, len(encodings)))).to(dev)
     n = args.eval_batch_size if encoding is None else encoding.shape[0]
     pipeline.set_progress_bar_config(disable=True)
-    images, (sample_rate, audios) = pipeline(generator=generator, batch_size=n, return_dict=False, encoding=encoding)
+    guide = {} if args.guidance_scale is None else {"guidance_scale": args.guidance_scale}   # unset: the call of before
+    images, (sample_rate, audios) = pipeline(generator=generator, batch_size=n, return_dict=False, encoding=encoding, **guide)
     d = os.path.join(output_dir, "samples")
     os.makedirs(d, exist_ok=True)
     for i, (image, audio) in enumerate(zip(images, audios)):
@@ -302,6 +331,11 @@ def parse_args(argv=None):
                         help="what the model is trained to predict; saved in scheduler/scheduler_config.json")
     parser.add_argument("--vae", type=str, default=None)
     parser.add_argument("--encodings", type=str, default=None)
+    parser.add_argument("--encoding_dropout", type=float, default=0.0,
+                        help="probability of training a sample on the zero encoding (needs --encodings): gives the model the "
+                             "unconditional branch that classifier-free guidance (guidance_scale > 1) samples against")
+    parser.add_argument("--guidance_scale", type=float, default=None,
+                        help="guidance scale of the sample images written during training (unset: unguided)")
     # additions (not in the reference)
     parser.add_argument("--resolution", type=int, default=256, help="image size of the synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=2048)

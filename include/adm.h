@@ -180,6 +180,30 @@ int adm_sched_step_pred(const float* x, const float* eps, const float* noise, fl
                         int B, int C, int H, int W, void* stream,
                         int lo, int hi, float w, float max_value, float* scale, int prediction);
 
+/* Classifier-free guidance (Ho & Salimans 2022; adm_version() >= 112). The model ran twice on the same x: eps_cond with the encoding,
+ * eps_uncond with the null encoding; the step and the selection use
+ *   o = eps_uncond + guidance_scale * (eps_cond - eps_uncond)      (three separately rounded fp32 operations, as diffusers' torch expression)
+ * wherever the entry points above use `eps`: in x0, in e and in the multistep history. One more operand in the same kernels: 16 B/elem where
+ * the unguided step moves 12 (+4 with noise, +8 with the history); each selection pass reads 12 B/elem instead of 8. eps_cond == eps_uncond
+ * (the same pointer, or equal values) gives the unguided result bit for bit at any finite scale. `prediction` as adm_sched_step_pred.
+ * adm_sched_threshold_guided: adm_sched_threshold_pred on |x0| of o.
+ * adm_sched_step_guided: hist != NULL: adm_sched_multistep (needs k_hist_table, prediction == 0 and scale == NULL); otherwise scale != NULL:
+ * adm_sched_step_thresholded; otherwise adm_sched_step (lo, hi, w, max_value ignored; k_hist_table ignored when hist == NULL).
+ * out may alias x; it must not alias eps_cond or eps_uncond's other samples (each lane reads its own elements before it writes them, so
+ * out == eps_cond or out == eps_uncond is in contract for the plain and multistep steps; the thresholded step's selection reads whole
+ * samples first, on the same stream, and is safe as well). A non-finite guidance_scale is refused; scale <= 1 is computed as asked
+ * (callers that follow diffusers' rule skip guidance there: u + 1*(c - u) is not c in floating point). */
+int adm_sched_threshold_guided(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale,
+                               const adm_sched_coef* coef_table, const int* step_dev, int step,
+                               int lo, int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W, void* stream,
+                               int prediction);
+int adm_sched_step_guided(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale, const float* noise,
+                          float* out, uint8_t* u8_out, const adm_sched_coef* coef_table, const float* k_hist_table, float* hist,
+                          const int* step_dev, int step,
+                          const float* mask, int n_mask_steps, int mask_start, int mask_end,
+                          int B, int C, int H, int W, void* stream,
+                          int lo, int hi, float w, float max_value, float* scale, int prediction);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -453,6 +477,18 @@ int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* c
                          const float* step_noise, const float* mask, int mask_start, int mask_end,
                          uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
                          int thresholded, int prediction);
+/* The sampling loops with classifier-free guidance (adm_sched_step_guided; adm_version() >= 112). The handle must be conditional and have
+ * an encoding set (adm_unet_set_encoding): that is the conditional branch. encoding_uncond_dev: device, the shape of the set encoding
+ * (B, seq_len, cross_attention_dim), the unconditional branch (zeros for a model trained with dropped encodings). Every step runs TWO forwards of
+ * batch B on the same plan, the second with the encoding pointer swapped and into a second output buffer that the handle allocates with its
+ * plan on the first guided call at a batch size, then one guided step kernel; all inside the one captured step. A sample's bits do not
+ * depend on its batch, and encoding_uncond_dev equal to the set encoding gives the unguided loop's bits. k_hist_host != NULL: the multistep
+ * loop (k_hist_host[0] == 0, prediction == 0, thresholded == 0); otherwise as adm_sample_loop_pred. The two encodings, the second buffer
+ * and the bits of guidance_scale are part of the captured graph's key. The handle's encoding is unchanged on return. */
+int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host, int n_steps,
+                           const float* step_noise, const float* mask, int mask_start, int mask_end,
+                           uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
+                           int thresholded, int prediction, const float* encoding_uncond_dev, float guidance_scale);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
