@@ -99,6 +99,9 @@ _SIGS = {
                                              C.c_float, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int]),
     "adm_sched_step_guided": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p] + [C.c_int] * 7 +
                               [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int]),
+    "adm_randn": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "adm_sched_step_philox": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_int] * 7 +
+                              [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint64, C.c_int]),
     "adm_noise_and_velocity": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_long, C.c_void_p]),
     "adm_add_noise": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                 C.c_int, C.c_int, C.c_long, C.c_void_p]),
@@ -158,6 +161,9 @@ _SIGS = {
     "adm_sample_loop_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), c_float_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_float]),
+    "adm_sample_loop_philox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_float, C.c_uint64, C.c_int]),
     "adm_encode_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_int, C.c_void_p]),
 }
 # entry points added by later translation units (k_mel.hip); bound when present in the header AND the library

@@ -45,6 +45,26 @@ def _guidance(eps, uncond, guidance_scale):
     return True
 
 
+def _seed64(seed, name="seed"):
+    """A noise-stream seed as the uint64 the C-ABI takes."""
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{name}={seed!r} must be in [0, 2^64)")
+    return seed
+
+
+def randn(shape, seed, row_offset=0, t=0, noise_stream=0, device=None):
+    """(B, C, H, W) normals of "adm noise stream 1" (include/adm.h; csrc/k_sched.hip `randn_fill_kernel`): Philox4x32-10 keyed by `seed`
+    on the counter (float4 index inside the sample, row_offset + b, t, noise_stream), two Box-Muller pairs per counter. Exactly what the
+    fused step draws for the same counters (noise_stream 0, t = the row's timestep); noise_stream 1 with t = 0 is the initial latent.
+    Its own stream: not torch.randn's on any device. C*H*W % 4 == 0."""
+    B, Cc, H, W = (int(v) for v in shape)
+    device = torch.device(device) if device is not None else N.default_device()
+    out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=device)
+    N.check(N.lib().adm_randn(N.ptr(out), B, Cc * H * W, _seed64(seed), int(row_offset), int(t), int(noise_stream), N.stream_for(out)))
+    return out
+
+
 def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None, prediction=0, uncond=None,
                     guidance_scale=None):
     """Per-sample dynamic threshold s_b = clamp(quantile(|x0_b|, ratio), 1, max_value) of x0 = (x - sqrt_beta*eps) / sqrt_alpha
@@ -71,17 +91,35 @@ def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, o
 
 
 def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
-               step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None):
+               step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None, noise_seed=None, noise_row_offset=0):
     """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194). x,eps: (B,C,H,W). threshold: None, or
     (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it instead of the static
     clamp (`adm_sched_step_thresholded`; scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device
     scalar that replaces `step`. prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model
     (`adm_sched_step_pred`; include/adm.h has the table). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional
-    model output and the step uses o = uncond + guidance_scale * (eps - uncond), combined inside the kernel (`adm_sched_step_guided`)."""
+    model output and the step uses o = uncond + guidance_scale * (eps - uncond), combined inside the kernel (`adm_sched_step_guided`).
+    noise_seed (instead of `noise`): a row with k_noise != 0 draws its noise inside the kernel from "adm noise stream 1" — `randn(x.shape,
+    noise_seed, noise_row_offset, t=the row's timestep)` without the tensor (`adm_sched_step_philox`); noise_row_offset is the global row
+    of x[0]."""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
+    if noise_seed is not None and noise is not None:
+        raise ValueError("`noise_seed` (noise drawn inside the kernel) and `noise=` (a noise tensor) exclude each other")
     out = torch.empty_like(x) if out is None else out
     n_mask = mask.shape[1] if mask is not None else 0
+    if noise_seed is not None:
+        guided = _guidance(eps, uncond, guidance_scale)
+        lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
+        if threshold is not None:
+            lo, hi, w = threshold_ranks(Cc * H * W, threshold[0])
+            max_value = threshold[1]
+            scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+        N.check(N.lib().adm_sched_step_philox(N.ptr(x), N.ptr(eps), N.ptr(uncond) if guided else None,
+                                              float(guidance_scale) if guided else 1.0, N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
+                                              N.ptr(step_dev), int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
+                                              N.stream_for(x), lo, hi, w, float(max_value), N.ptr(scale), int(prediction),
+                                              _seed64(noise_seed, "noise_seed"), int(noise_row_offset)))
+        return out
     if _guidance(eps, uncond, guidance_scale):
         lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
         if threshold is not None:

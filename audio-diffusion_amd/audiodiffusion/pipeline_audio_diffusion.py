@@ -190,13 +190,29 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         buf = keep.copy_(neg) if fits else neg.contiguous().clone()
         return buf, buf
 
+    @staticmethod
+    def _device_noise(device_noise_seed, **excluded):
+        """The rule of `device_noise_seed` (`__call__`): it replaces every other source of noise, so none may be given with it."""
+        if device_noise_seed is None:
+            return
+        ops._seed64(device_noise_seed, "device_noise_seed")
+        for name, given in excluded.items():
+            if given is not None:
+                raise ValueError(f"device_noise_seed draws the noise on the device from its own stream: it cannot be combined with `{name}`")
+
     def _denoise(self, images, start_step, eta, step_generator, mask, mask_start, mask_end, step_noise=None,
-                 use_graph=True, want_u8=True, encoding=None, stop_step=None, guidance_scale=None, negative_encoding=None):
+                 use_graph=True, want_u8=True, encoding=None, stop_step=None, guidance_scale=None, negative_encoding=None,
+                 device_noise_seed=None, device_noise_row_offset=0):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
         before that step index, so that a single step of a long schedule can be compared in isolation.
         guidance_scale > 1: every step is two forwards (the encoding, the negative encoding) and one guided step kernel, inside the
-        same native call (`adm_sample_loop_guided`); otherwise today's entry points, one forward per step."""
+        same native call (`adm_sample_loop_guided`); otherwise today's entry points, one forward per step.
+        device_noise_seed: the noise of every noisy row is drawn inside the step kernel ("adm noise stream 1", include/adm.h) at (seed,
+        device_noise_row_offset + b, the row's timestep): ONE native call (`adm_sample_loop_philox`) whatever the number of steps, no
+        staging tensor, no chunks, no synchronisation. A schedule without noisy rows (DDIM with eta == 0, the multistep solver) takes
+        today's entry points."""
         sched, unet = self.scheduler, self.unet
+        self._device_noise(device_noise_seed, step_generator=step_generator, step_noise=step_noise)
         guided = self._guided(guidance_scale, negative_encoding, encoding)
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
         thresh = None if multistep else sched.threshold()
@@ -219,7 +235,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         if Cc != 1 and want_u8:
             u8 = None  # NHWC permute for multi-channel images is done after the loop
         needs_noise = [r["k_noise"] != 0.0 for r in rows]
-        chunk = n if not any(needs_noise) else min(n, self._STEP_CHUNK)
+        philox = device_noise_seed is not None and any(needs_noise)
+        chunk = n if philox or not any(needs_noise) else min(n, self._STEP_CHUNK)
         stage = None
         done = 0
         while done < n:
@@ -229,7 +246,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                                        ("sqrt_beta", "sqrt_alpha", "clip", "k_x0", "k_x", "k_eps", "k_noise", "timestep")])
                                        for r in sub])
             noise_ptr = None
-            if any(needs_noise[done:done + m]):
+            if not philox and any(needs_noise[done:done + m]):
                 if stage is None or stage.shape[0] != m:
                     stage = torch.empty((m, B, Cc, H, W), dtype=torch.float32, device=x.device)
                 for i in range(m):
@@ -246,7 +263,16 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 mask_chunk = mask[:, done:done + m].contiguous()
                 mask_ptr = N.ptr(mask_chunk)
             u8_ptr = N.ptr(u8) if (last and u8 is not None) else None
-            if guided:   # every mode through the one guided entry point; the multistep loop stays one call
+            if philox:   # noise drawn in the step kernel: plain / thresholded, any prediction type, guided or not, all steps at once
+                assert m == n and not multistep
+                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
+                N.check(N.lib().adm_sample_loop_philox(h, N.ptr(x), B, coef, m, mask_ptr, int(mask_start), int(mask_end), u8_ptr,
+                                                       int(use_graph), N.stream_for(x), lo, hi, w,
+                                                       thresh[1] if thresh is not None else 1.0, int(thresh is not None), pred,
+                                                       N.ptr(unet._enc_uncond) if guided else None,
+                                                       float(guidance_scale) if guided else 1.0,
+                                                       ops._seed64(device_noise_seed, "device_noise_seed"), int(device_noise_row_offset)))
+            elif guided:   # every mode through the one guided entry point; the multistep loop stays one call
                 assert not multistep or m == n
                 khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub]) if multistep else None
                 lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
@@ -300,6 +326,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         init_phase=None,
         guidance_scale=None,
         negative_encoding=None,
+        device_noise_seed: int = None,
+        device_noise_row_offset: int = 0,
     ) -> Union[PipelineOutput, Tuple[List[Image.Image], Tuple[int, List[np.ndarray]]]]:
         """Generate random mel spectrogram from audio input and convert to audio (reference docstring `:89-112`).
 
@@ -315,14 +343,26 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             model on the encoding (c) and on the negative encoding (u) and steps with u + g*(c - u), all inside the captured loop.
           * `negative_encoding` None means zeros of the encoding's shape (what `train_unet.py --encoding_dropout` trains the model
             to read as "no condition"); otherwise it must have the encoding's shape, a leading 1 being broadcast over the batch.
-          * a `negative_encoding` without g > 1 is a ValueError."""
+          * a `negative_encoding` without g > 1 is a ValueError.
+
+        Device noise, off by default: `device_noise_seed` (an int in [0, 2^64)). All noise then comes from "adm noise stream 1"
+        (include/adm.h): a counter-based generator evaluated on the device, a pure function of (seed, global sample row, timestep,
+        element). The initial latent, unless `noise` is given, is `ops.randn(..., noise_stream=1)`; every noisy step (DDPM, DDIM with
+        eta > 0) draws inside the fused step kernel, and the loop is one native call without a noise tensor. Sample b is global row
+        `device_noise_row_offset` + b, so a sample's bits depend on neither its batch nor its shard. It is NOT torch.randn's stream: the
+        same seed gives other images than a torch generator. With `generator`, `step_generator` or `step_noise` it is a ValueError; with
+        the multistep scheduler (no noisy steps) the seed only picks the initial latent."""
         self._guided(guidance_scale, negative_encoding, encoding)   # the ValueErrors, before any work
+        self._device_noise(device_noise_seed, generator=generator, step_generator=step_generator, step_noise=step_noise)
         steps = steps or self.get_default_steps()
         self.scheduler.set_timesteps(steps)
         step_generator = step_generator or generator
         # For backwards compatibility
         if type(self.unet.sample_size) == int:
             self.unet.sample_size = (self.unet.sample_size, self.unet.sample_size)
+        if noise is None and device_noise_seed is not None:
+            noise = ops.randn((batch_size, self.unet.in_channels, self.unet.sample_size[0], self.unet.sample_size[1]), device_noise_seed,
+                              row_offset=device_noise_row_offset, t=0, noise_stream=1, device=self.device)
         if noise is None:
             # the reference's torch.randn(..., generator=generator, device=self.device) (:120-128); going through
             # randn_tensor additionally accepts a CPU generator on the GPU build (drawn on the host, then moved)
@@ -361,7 +401,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         use_mask = mask if (mask is not None and (mask_start > 0 or mask_end > 0)) else None
         images, u8 = self._denoise(images, start_step, eta, step_generator, use_mask, mask_start, mask_end,
                                    step_noise=step_noise, want_u8=self.vqvae is None, encoding=encoding,
-                                   guidance_scale=guidance_scale, negative_encoding=negative_encoding)
+                                   guidance_scale=guidance_scale, negative_encoding=negative_encoding,
+                                   device_noise_seed=device_noise_seed, device_noise_row_offset=device_noise_row_offset)
 
         if self.vqvae is not None:
             # 0.18215 was scaling factor used in training to ensure unit variance (pipeline:187-190); the 1/0.18215

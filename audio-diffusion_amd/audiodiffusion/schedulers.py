@@ -19,6 +19,9 @@ there, an epsilon scheduler refuses such a schedule. The multistep scheduler sta
 Classifier-free guidance: `step(..., model_output_uncond=u, guidance_scale=g)` of the three schedulers takes the conditional output as
 `model_output` and steps with u + g*(model_output - u), combined inside the one fused kernel (`adm_sched_step_guided`; the
 thresholded and the multistep paths included). Both keywords or neither; the `<= 1 means off` rule belongs to the pipeline.
+Device noise: `step(..., device_noise_seed=s, device_noise_row_offset=r)` (DDPM, DDIM with eta > 0) draws the step's noise inside the fused
+kernel from "adm noise stream 1" (include/adm.h) at (seed s, global row r + b, the step's timestep) instead of `randn_tensor`
+(`adm_sched_step_philox`). Not together with `generator` or `variance_noise`.
 """
 import json
 import math
@@ -247,17 +250,22 @@ class _SchedulerBase:
             return None
         return float(self.config.dynamic_thresholding_ratio), float(self.config.sample_max_value)
 
-    def _step(self, model_output, timestep, sample, eta, generator, variance_noise, model_output_uncond=None, guidance_scale=None):
+    def _step(self, model_output, timestep, sample, eta, generator, variance_noise, model_output_uncond=None, guidance_scale=None,
+              device_noise_seed=None, device_noise_row_offset=0):
+        if device_noise_seed is not None:
+            for name, given in (("generator", generator), ("variance_noise", variance_noise)):
+                if given is not None:
+                    raise ValueError(f"device_noise_seed draws the step noise inside the kernel: it cannot be combined with `{name}`")
         i = self._index_of(timestep)
         _, table, rows = self._cached(sample.device, eta)
         need_noise = rows[i]["k_noise"] != 0.0
-        if need_noise and variance_noise is None:
+        if need_noise and variance_noise is None and device_noise_seed is None:
             variance_noise = randn_tensor(model_output.shape, generator, model_output.device, model_output.dtype)
         prev = ops.sched_step(sample.contiguous(), model_output.contiguous(), table, i,
                               noise=variance_noise.contiguous() if variance_noise is not None else None,
                               threshold=self.threshold(), prediction=self.prediction,
                               uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
-                              guidance_scale=guidance_scale)
+                              guidance_scale=guidance_scale, noise_seed=device_noise_seed, noise_row_offset=device_noise_row_offset)
         return SchedulerOutput(prev_sample=prev)
 
 
@@ -293,8 +301,9 @@ class DDPMScheduler(_SchedulerBase):
         return rows
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None, *,
-             model_output_uncond=None, guidance_scale=None):
-        return self._step(model_output, timestep, sample, 0.0, generator, variance_noise, model_output_uncond, guidance_scale)
+             model_output_uncond=None, guidance_scale=None, device_noise_seed=None, device_noise_row_offset=0):
+        return self._step(model_output, timestep, sample, 0.0, generator, variance_noise, model_output_uncond, guidance_scale,
+                          device_noise_seed, device_noise_row_offset)
 
 
 class DDIMScheduler(_SchedulerBase):
@@ -339,10 +348,12 @@ class DDIMScheduler(_SchedulerBase):
         return rows
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
-             variance_noise=None, return_dict=True, *, model_output_uncond=None, guidance_scale=None):
+             variance_noise=None, return_dict=True, *, model_output_uncond=None, guidance_scale=None, device_noise_seed=None,
+             device_noise_row_offset=0):
         if use_clipped_model_output:
             raise NotImplementedError("use_clipped_model_output is not implemented (the reference never sets it)")
-        return self._step(model_output, timestep, sample, float(eta), generator, variance_noise, model_output_uncond, guidance_scale)
+        return self._step(model_output, timestep, sample, float(eta), generator, variance_noise, model_output_uncond, guidance_scale,
+                          device_noise_seed, device_noise_row_offset)
 
 
 def _f32(v):

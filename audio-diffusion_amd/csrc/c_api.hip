@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 112; }   // 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 113; }   // 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -175,6 +175,27 @@ int adm_sched_step_guided(const float* x, const float* eps_cond, const float* ep
     p.hist = hist; p.k_hist_table = k_hist_table;
     return launch_sched_step(p, SCHED_MULTISTEP, (hipStream_t)stream);
   }
+  if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
+  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
+  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);
+}
+
+int adm_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, void* stream) {
+  return launch_randn(out, B, per_sample, seed, row_offset, t, noise_stream, (hipStream_t)stream);
+}
+
+int adm_sched_step_philox(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale, float* out, uint8_t* u8_out,
+                          const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask, int n_mask_steps,
+                          int mask_start, int mask_end, int B, int C, int H, int W, void* stream, int lo, int hi, float w, float max_value,
+                          float* scale, int prediction, uint64_t seed, int row_offset) {
+  ADM_REQUIRE(x && eps_cond && out && coef_table, "sched_step_philox: null argument");
+  ADM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "sched_step_philox: bad shape");
+  ADM_REQUIRE(row_offset >= 0, "sched_step_philox: row_offset must be >= 0");
+  ADM_REQUIRE((uint64_t)row_offset + (uint64_t)B <= 0xffffffffull, "sched_step_philox: row_offset + B must fit in 32 bits");
+  SchedStepParams p{x, eps_cond, nullptr, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
+  p.eps_uncond = eps_uncond; p.guidance = guidance_scale;
+  p.philox = 1;
+  p.nvals[0] = (uint32_t)(seed & 0xffffffffull); p.nvals[1] = (uint32_t)(seed >> 32); p.nvals[2] = (uint32_t)row_offset; p.nvals[3] = 0;
   if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
   p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
   return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);

@@ -1,7 +1,8 @@
 // k_sched.hip — fused scheduler epilogue, add_noise and u8 dequantisation (HBM-bound elementwise).
 // Replaces DDIMScheduler.step / DDPMScheduler.step + mask overwrite + final dequant
 // (reference: audiodiffusion/pipeline_audio_diffusion.py:165-185,192-194; SURVEY.md §8(a) S2-S4,P4,P5).
-// One float4 per lane per iteration, grid-stride; algorithmic bytes: 12 B/elem (x, eps in; out) +4 with noise.
+// One float4 per lane per iteration, grid-stride; algorithmic bytes: 12 B/elem (x, eps in; out), +4 with a noise BUFFER, +0 with noise
+// drawn in the kernel (the noise stream below): a noisy step moves 12 B/elem instead of 16 (guided: 16 instead of 20).
 // sched_step_kernel<MODE> is ONE kernel for the three steps; the loop, the noise slice, the mask overwrite and the u8 pack are shared and only
 // the handful of lines that compute x0 and the update depend on MODE:
 //   SCHED_PLAIN      DDIM / DDPM with the row's static clamp.
@@ -22,6 +23,15 @@
 // float4 load per lane: 16 B/elem where the unguided step moves 12 (+4 with noise, +8 with the multistep history, as before); every pass of
 // the selection reads 12 B/elem instead of 8. sched_step_guided_kernel<MODE, PRED> / sched_threshold_guided_kernel<PRED>: plain and
 // thresholded for the three prediction types, multistep for epsilon. The unguided kernels keep their names and their arithmetic.
+// Noise has three sources: none, a buffer (p.noise), and "adm noise stream 1" (include/adm.h): Philox4x32-10 keyed by the seed and counted
+// by (float4 index inside the sample, global sample row, timestep, stream id), turned into four normals by two Box-Muller pairs, drawn by
+// the lane that consumes them. noise_stream_normals is the ONE helper for randn_fill_kernel (the initial latent, and what tests
+// materialise) and for the step body. The source is a TEMPLATE parameter (PHILOX, the fourth of sched_step_body), not a runtime branch:
+// the 14 instantiations that existed before it (3 sched_step_kernel, 4 sched_step_pred_kernel, 7 sched_step_guided_kernel) compile without
+// a line of the generator and keep their registers and their arithmetic; sched_step_philox_kernel<MODE, PRED, GUIDED> adds 12 (plain and
+// thresholded, three prediction types, guided or not; the multistep step has no noise rows): 26 step kernels in all. In the captured loop
+// the key, the row offset and the stream id are read from a 16-byte device block (p.nblock), as the step index is read from *step_dev, so a
+// new seed or shard offset replays the same graph; the eager entry point passes them by value (p.nvals).
 #include "adm_kernels.h"
 #include <cmath>
 
@@ -60,6 +70,42 @@ __device__ __forceinline__ float sched_guided(float u, float c, float g) {
   return u + gd;
 }
 
+// ---- "adm noise stream 1" (include/adm.h) -----------------------------------------------------------------------------------------
+// The high half of a 32 x 32 product, in plain C++ (the compiler picks v_mul_hi_u32; the emulator multiplies in 64 bits).
+__device__ __forceinline__ uint32_t noise_mulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+
+// Box-Muller on two 32-bit words: u1 = ((a >> 8) + 1) * 2^-24 in (0, 1], u2 = (b >> 8) * 2^-24 in [0, 1), both exact in fp32;
+// (z0, z1) = sqrt(-2 ln u1) * (cos 2 pi u2, sin 2 pi u2). |z| <= sqrt(48 ln 2) < 5.77. Products only, each feeding a function or another
+// product, under `fp contract(off)`: there is nothing to fuse, so the bits depend on no contraction setting and on no inlining context.
+__device__ __forceinline__ void noise_box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
+#pragma clang fp contract(off)
+  const float u1 = (float)((a >> 8) + 1u) * 5.9604644775390625e-8f;
+  const float u2 = (float)(b >> 8) * 5.9604644775390625e-8f;
+  const float m = -2.f * logf(u1);
+  const float r = sqrtf(m);
+  const float th = 6.283185307179586f * u2;
+  const float cs = cosf(th), sn = sinf(th);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+// The four normals of elements 4q .. 4q+3 of global sample row `row` at integer timestep `t` of stream `sid`: Philox4x32-10 (Salmon et al.
+// 2011) with key (k0, k1) = (seed & 0xffffffff, seed >> 32) on the counter (q, row, t, sid); (z0, z1) = BM(r0, r1), (z2, z3) = BM(r2, r3).
+__device__ __forceinline__ float4 noise_stream_normals(uint32_t k0, uint32_t k1, uint32_t q, uint32_t row, uint32_t t, uint32_t sid) {
+  uint32_t c0 = q, c1 = row, c2 = t, c3 = sid;
+  ADM_UNROLL
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = noise_mulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = noise_mulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  float4 z;
+  noise_box_muller(c0, c1, z.x, z.y);
+  noise_box_muller(c2, c3, z.z, z.w);
+  return z;
+}
+
 __device__ __forceinline__ unsigned char quant_u8(float v) {
   float q = fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f) * 255.f;
   return (unsigned char)rintf(q);  // round-half-even == numpy .round() (pipeline:194)
@@ -79,16 +125,26 @@ __device__ __forceinline__ unsigned pack_u8x4(float a, float b, float c, float d
 //                    (0 * NaN must not reach the output). Each lane reads and rewrites its own elements of hist.
 // PRED: what p.eps holds (the model output o); e below is sched_eps of it, the model output itself for PRED_EPSILON.
 // GUIDED: p.eps is the conditional output and o = sched_guided(p.eps_uncond, p.eps, p.guidance): in x0, in e and so in the history m0.
+// PHILOX: the noise of a row with k_noise != 0 is noise_stream_normals of (q, row) = (i % (per_sample/4), row offset + i / (per_sample/4))
+// at the row's integer timestep, and p.noise is not read; a row with k_noise == 0 draws nothing (the branch is uniform over the grid).
 // out may alias x.
 // first, stride: the lane's first float4 and the grid's stride, which the kernel works out itself (a launch-geometry builtin is only
 // folded against the kernel's launch bounds where the kernel reads it).
-template <int MODE, int PRED, bool GUIDED>
+template <int MODE, int PRED, bool GUIDED, bool PHILOX = false>
 __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const long first, const long stride) {
+  static_assert(!PHILOX || MODE != SCHED_MULTISTEP, "the multistep step has no noise rows");
   const int s = p.step_dev ? *p.step_dev : p.step;
   const adm_sched_coef c = p.table[s];
   const float k_hist = MODE == SCHED_MULTISTEP ? p.k_hist_table[s] : 0.f;
   const bool use_hist = k_hist != 0.f;
-  const bool use_noise = p.noise != nullptr && c.k_noise != 0.f;
+  const bool use_noise = (PHILOX || p.noise != nullptr) && c.k_noise != 0.f;
+  uint32_t nk0 = 0, nk1 = 0, nrow0 = 0, nsid = 0, nt = 0;
+  const long n4s = p.per_sample >> 2;   // float4 per sample
+  if (PHILOX) {
+    nk0 = p.nblock ? p.nblock[0] : p.nvals[0]; nk1 = p.nblock ? p.nblock[1] : p.nvals[1];
+    nrow0 = p.nblock ? p.nblock[2] : p.nvals[2]; nsid = p.nblock ? p.nblock[3] : p.nvals[3];
+    nt = (uint32_t)(int)c.timestep;
+  }
   const float* noise = p.noise + (long)s * p.noise_step_stride;  // per-step slice of a (n_steps,B,C,H,W) noise tensor (0: single step)
   unsigned char* u8 = p.u8_step >= 0 && s != p.u8_step ? nullptr : p.u8;
   for (long i = first; i < p.n4; i += stride) {
@@ -100,7 +156,12 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
                        sched_guided(uv.w, ev.w, p.guidance));
     }
     float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
+    if (PHILOX) {
+      if (use_noise) {
+        const long row = i / n4s;
+        nv = noise_stream_normals(nk0, nk1, (uint32_t)(i - row * n4s), nrow0 + (uint32_t)row, nt, nsid);
+      }
+    } else if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
     if (use_hist) hv = reinterpret_cast<const float4*>(p.hist)[i];
     float th = 0.f;
     if (MODE == SCHED_THRESH) th = p.scale[(i * 4) / p.per_sample];  // W % 4 == 0: a float4 never straddles two samples
@@ -156,6 +217,21 @@ template <int MODE, int PRED>
 __global__ void __launch_bounds__(256) sched_step_guided_kernel(const SchedStepParams p) {
   static_assert(MODE != SCHED_MULTISTEP || PRED == PRED_EPSILON, "the multistep step is epsilon only");
   sched_step_body<MODE, PRED, true>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+template <int MODE, int PRED, bool GUIDED>
+__global__ void __launch_bounds__(256) sched_step_philox_kernel(const SchedStepParams p) {
+  sched_step_body<MODE, PRED, GUIDED, true>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+// (B, per_sample) normals of the stream at one (t, stream id): out[b][4q .. 4q+3] = noise_stream_normals(q, row_offset + b). One float4 per lane.
+__global__ void __launch_bounds__(256) randn_fill_kernel(float* __restrict__ out, long n4, long n4s, uint32_t k0, uint32_t k1,
+                                                         uint32_t row0, uint32_t t, uint32_t sid) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const long row = i / n4s;
+    reinterpret_cast<float4*>(out)[i] = noise_stream_normals(k0, k1, (uint32_t)(i - row * n4s), row0 + (uint32_t)row, t, sid);
+  }
 }
 
 // ---- dynamic threshold: exact per-sample order statistics of |x0| ---------------------------------------------------------------------
@@ -417,6 +493,33 @@ int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coe
   return ADM_CHECK_LAUNCH();
 }
 
+int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, hipStream_t st) {
+  ADM_REQUIRE(out != nullptr && B > 0, "randn: null output or B <= 0");
+  ADM_REQUIRE(per_sample > 0 && per_sample % 4 == 0, "randn: per_sample must be a positive multiple of 4");
+  ADM_REQUIRE(per_sample / 4 <= 0xffffffffL, "randn: per_sample / 4 must fit in 32 bits (the counter's first word)");
+  ADM_REQUIRE(row_offset >= 0, "randn: row_offset must be >= 0");
+  ADM_REQUIRE((uint64_t)row_offset + (uint64_t)B <= 0xffffffffull, "randn: row_offset + B must fit in 32 bits");
+  ADM_REQUIRE(t >= 0, "randn: the timestep must be in [0, 2^31)");
+  ADM_REQUIRE(noise_stream == 0 || noise_stream == 1, "randn: noise_stream must be 0 (step noise) or 1 (initial latent); 2 and 3 are reserved");
+  const long n4s = per_sample / 4, n4 = n4s * B;
+  ADM_LAUNCH(randn_fill_kernel, dim3(ew_grid(n4)), dim3(256), 0, st, out, n4, n4s, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32),
+             (uint32_t)row_offset, (uint32_t)t, (uint32_t)noise_stream);
+  return ADM_CHECK_LAUNCH();
+}
+
+template <int MODE>
+static int launch_philox_step(const SchedStepParams& p, dim3 grid, dim3 block, hipStream_t st, int pred, bool guided) {
+  if (guided) {
+    if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_SAMPLE, true>), grid, block, 0, st, p);
+    else if (pred == PRED_V) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_V, true>), grid, block, 0, st, p);
+    else ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_EPSILON, true>), grid, block, 0, st, p);
+  }
+  else if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_SAMPLE, false>), grid, block, 0, st, p);
+  else if (pred == PRED_V) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_V, false>), grid, block, 0, st, p);
+  else ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_EPSILON, false>), grid, block, 0, st, p);
+  return ADM_CHECK_LAUNCH();
+}
+
 // SCHED_THRESH: selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written
 int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int pred) {
   ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_step: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
@@ -428,6 +531,20 @@ int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int p
   const dim3 grid(ew_grid(p.n4)), block(256);
   const bool guided = p.eps_uncond != nullptr;
   if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_step: the guidance scale must be finite");
+  if (p.philox) {   // noise drawn in the kernel: the key, row offset and stream id from *p.nblock, or from p.nvals when it is null
+    ADM_REQUIRE(mode == SCHED_PLAIN || mode == SCHED_THRESH, "sched_step_philox: the multistep step has no noise rows");
+    ADM_REQUIRE(p.noise == nullptr, "sched_step_philox: a noise buffer and the noise stream exclude each other");
+    ADM_REQUIRE(p.B > 0 && p.per_sample > 0 && p.per_sample % 4 == 0, "sched_step_philox: C*H*W must be a positive multiple of 4");
+    ADM_REQUIRE(p.W % 4 == 0, "sched_step_philox: W must be a multiple of 4");
+    ADM_REQUIRE(p.per_sample / 4 <= 0xffffffffL, "sched_step_philox: C*H*W / 4 must fit in 32 bits (the counter's first word)");
+    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_philox: mask path requires C == 1 (as in the reference)");
+    if (mode == SCHED_THRESH) {
+      ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,
+                                     p.W, st, pred, p.eps_uncond, p.guidance));
+      return launch_philox_step<SCHED_THRESH>(p, grid, block, st, pred, guided);
+    }
+    return launch_philox_step<SCHED_PLAIN>(p, grid, block, st, pred, guided);
+  }
   if (mode == SCHED_THRESH) {
     ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_thresholded: mask path requires C == 1 (as in the reference)");
     ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,

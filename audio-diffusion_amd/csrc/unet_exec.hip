@@ -45,6 +45,10 @@ struct adm_unet {
   float* khist_dev = nullptr;    // per-step history coefficient of the multistep loop, beside coef_dev
   int khist_cap = 0;
   int* step_dev = nullptr;
+  // the noise-stream block of adm_sample_loop_philox: {seed_lo, seed_hi, row_offset, stream id}. Allocated once and never moved (its address
+  // is in the captured graph's key); rewritten from noise_blk_host by a stream-ordered copy before every run.
+  uint32_t* noise_blk_dev = nullptr;
+  uint32_t noise_blk_host[4] = {0, 0, 0, 0};
   // training
   bool training = false;
   int warm_B = 0;         // batch size at which an uncaptured forward has already run (see run_loop)
@@ -348,7 +352,18 @@ struct LoopArgs {
   int pred = PRED_EPSILON;                                    // what the model output is: chooses the step (and selection) kernel
   // classifier-free guidance (both set, or neither): the unconditional encoding, device, of the shape of the handle's encoding, and the scale
   const float* ctx_uncond = nullptr; float guidance = 1.f;
+  // noise drawn inside the step kernel ("adm noise stream 1"): the seed and the global row of x[0]. They reach the kernel through the
+  // handle's device block, never as kernel arguments: neither is part of the captured graph's key.
+  bool philox = false; uint64_t seed = 0; int row_offset = 0;
 };
+
+// The noise-stream block, written in stream order before the first step and outside the captured step.
+static int ensure_noise_block(adm_unet* h, const LoopArgs& a, hipStream_t st) {
+  if (h->noise_blk_dev == nullptr) ADM_TRY(dalloc(h, (void**)&h->noise_blk_dev, sizeof(h->noise_blk_host)));
+  h->noise_blk_host[0] = (uint32_t)(a.seed & 0xffffffffull); h->noise_blk_host[1] = (uint32_t)(a.seed >> 32);
+  h->noise_blk_host[2] = (uint32_t)a.row_offset; h->noise_blk_host[3] = 0;   // stream 0: step noise
+  return copy_h2d(h->noise_blk_dev, h->noise_blk_host, sizeof(h->noise_blk_host), st);
+}
 
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
 static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st) {
@@ -375,6 +390,7 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
     p.lo = a.th_lo; p.hi = a.th_hi; p.w = a.th_w; p.max_value = a.th_max; p.scale = h->scale_buf;
     p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
     if (a.ctx_uncond != nullptr) { p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance; }
+    if (a.philox) { p.philox = 1; p.nblock = h->noise_blk_dev; }
     ADM_TRY(launch_sched_step(p, a.mode, st, a.pred));
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
@@ -392,6 +408,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
+  if (a.philox) ADM_TRY(ensure_noise_block(h, a, st));
   for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
   return 0;
 #else
@@ -406,6 +423,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
   }
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, run));
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
+  if (a.philox) ADM_TRY(ensure_noise_block(h, a, run));
   if (!use_graph) {
     for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
   } else {
@@ -425,6 +443,8 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
       memcpy(&gb, &a.guidance, 4);
       key.push_back((uint64_t)a.ctx_uncond); key.push_back((uint64_t)h->eps_uncond_buf); key.push_back(0x100000000ull | gb);
     }
+    // the noise stream: the block's address (the handle's, stable) and nothing else; the seed and the row offset are data behind it
+    if (a.philox) { key.push_back(0x200000000ull); key.push_back((uint64_t)h->noise_blk_dev); }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
         // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
@@ -756,6 +776,32 @@ int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef*
   if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
   a.pred = prediction;
   a.ctx_uncond = encoding_uncond_dev; a.guidance = guidance_scale;
+  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+}
+
+int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, const float* mask, int mask_start,
+                           int mask_end, uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
+                           int thresholded, int prediction, const float* encoding_uncond_dev, float guidance_scale, uint64_t seed,
+                           int row_offset) {
+  ADM_REQUIRE(h && x && coef_host && n_steps > 0 && B > 0, "sample_loop_philox: bad argument");
+  ADM_REQUIRE(prediction >= PRED_EPSILON && prediction <= PRED_V,
+              "sample_loop_philox: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  ADM_REQUIRE(row_offset >= 0, "sample_loop_philox: row_offset must be >= 0");
+  ADM_REQUIRE((uint64_t)row_offset + (uint64_t)B <= 0xffffffffull, "sample_loop_philox: row_offset + B must fit in 32 bits");
+  ADM_REQUIRE(((long)h->cfg.in_channels * h->cfg.sample_h * h->cfg.sample_w) % 4 == 0,
+              "sample_loop_philox: C*H*W must be a multiple of 4");
+  for (int i = 0; i < n_steps; ++i)   // the counter's third word is the row's timestep as an integer
+    ADM_REQUIRE(coef_host[i].timestep >= 0.f && coef_host[i].timestep < 2147483648.f, "sample_loop_philox: every timestep must be in [0, 2^31)");
+  LoopArgs a{x, B, n_steps, nullptr, mask, mask_start, mask_end, u8_out, thresholded ? SCHED_THRESH : SCHED_PLAIN, nullptr};
+  if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
+  a.pred = prediction;
+  if (encoding_uncond_dev != nullptr) {   // guided, as adm_sample_loop_guided; NULL: unguided, and the model may be unconditional
+    ADM_REQUIRE(h->cfg.cross_attention_dim > 0, "sample_loop_philox: this model has no cross-attention (UNet2DModel): nothing to guide");
+    ADM_REQUIRE(h->net.ctx != nullptr && h->net.ctx_S > 0, "sample_loop_philox: no encoding set (adm_unet_set_encoding)");
+    ADM_REQUIRE(std::isfinite(guidance_scale), "sample_loop_philox: the guidance scale must be finite");
+    a.ctx_uncond = encoding_uncond_dev; a.guidance = guidance_scale;
+  }
+  a.philox = true; a.seed = seed; a.row_offset = row_offset;
   return run_loop_fp32(h, a, coef_host, use_graph, stream);
 }
 

@@ -204,6 +204,38 @@ int adm_sched_step_guided(const float* x, const float* eps_cond, const float* ep
                           int B, int C, int H, int W, void* stream,
                           int lo, int hi, float w, float max_value, float* scale, int prediction);
 
+/* Noise drawn on the device, inside the kernel that consumes it (adm_version() >= 113).
+ *
+ * "adm noise stream 1": a normal is a pure function of (seed, global sample row, integer timestep, element, stream id). It is its own
+ * definition; it does not reproduce torch.randn on any device.
+ *   generator  Philox4x32-10 (Salmon et al. 2011, "Parallel random numbers: as easy as 1, 2, 3"): multipliers 0xD2511F53, 0xCD9E8D57, key
+ *              increments 0x9E3779B9, 0xBB67AE85; key = (seed & 0xffffffff, seed >> 32) of a uint64 seed.
+ *   counter    (q, row, t, stream):  q = element index / 4, element index = c*H*W + y*W + x inside the sample (the index of the float4);
+ *              row = row_offset + b, the GLOBAL sample row;  t = the row's adm_sched_coef.timestep converted to an integer (not the loop's
+ *              step index);  stream = 0 step noise, 1 initial latent (t = 0), 2 and 3 reserved (VAE posterior, training noise; not built).
+ *   normals    the four outputs r0..r3 give the normals of elements 4q .. 4q+3:  (z0, z1) = BM(r0, r1), (z2, z3) = BM(r2, r3) with
+ *              BM(a, b): u1 = ((a >> 8) + 1) * 2^-24 in (0, 1], u2 = (b >> 8) * 2^-24 in [0, 1) (both exact in fp32),
+ *                        R = sqrt(-2 ln u1),  result (R cos 2 pi u2, R sin 2 pi u2).   |z| <= sqrt(48 ln 2) < 5.77: always finite.
+ * Within one build of the library every kernel that draws from the stream gives the same bits (one device helper); two builds (gfx950, the
+ * CPU emulation) agree to the accuracy of their logf / sinf / cosf, not bit for bit. So a sample's bits depend on neither its batch, its
+ * shard, a chunking of the steps nor the step a run starts at.
+ *
+ * adm_randn: out (B, per_sample) device floats = the normals of rows row_offset .. row_offset + B - 1 at (t, noise_stream); what the step
+ * kernel draws for the same counters, materialised. per_sample % 4 == 0, row_offset >= 0, row_offset + B within 32 bits, t in [0, 2^31),
+ * noise_stream 0 or 1.
+ * adm_sched_step_philox: adm_sched_step_guided's step (scale == NULL: the static clip; otherwise thresholded) with the noise of a row with
+ * k_noise != 0 drawn in the kernel from (seed, row_offset + b, timestep of the row, element) of stream 0 instead of read from a buffer:
+ * 12 B/elem where the buffer costs 16 (guided: 16 instead of 20). eps_uncond == NULL: unguided (guidance_scale is ignored). A row with
+ * k_noise == 0 draws nothing and equals the step without noise. There is no multistep form: that step has no noise rows. */
+int adm_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, void* stream);
+int adm_sched_step_philox(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale,
+                          float* out, uint8_t* u8_out, const adm_sched_coef* coef_table,
+                          const int* step_dev, int step,
+                          const float* mask, int n_mask_steps, int mask_start, int mask_end,
+                          int B, int C, int H, int W, void* stream,
+                          int lo, int hi, float w, float max_value, float* scale, int prediction,
+                          uint64_t seed, int row_offset);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -489,6 +521,18 @@ int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef*
                            const float* step_noise, const float* mask, int mask_start, int mask_end,
                            uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
                            int thresholded, int prediction, const float* encoding_uncond_dev, float guidance_scale);
+/* adm_sample_loop_pred / adm_sample_loop_guided with the step noise drawn inside the step kernel (adm_sched_step_philox; adm_version() >=
+ * 113): no noise tensor, whatever n_steps. row_offset: the global row of x[0] (a shard's first row). encoding_uncond_dev == NULL: unguided,
+ * and the model may be unconditional; otherwise as adm_sample_loop_guided. The handle owns a 16-byte device block {seed_lo, seed_hi,
+ * row_offset, stream id} that the step kernel reads through a pointer, as it reads the step index; this call rewrites it with a
+ * stream-ordered copy before the first step, outside the captured step. The captured graph's key gains that block's address (stable for
+ * the life of the handle) and nothing else: another seed or another row_offset replays the same graph. Every coef_host[i].timestep must be
+ * in [0, 2^31). */
+int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
+                           const float* mask, int mask_start, int mask_end,
+                           uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
+                           int thresholded, int prediction, const float* encoding_uncond_dev, float guidance_scale,
+                           uint64_t seed, int row_offset);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
