@@ -41,6 +41,30 @@ class ConvArgs(C.Structure):
     ]
 
 
+class SchedStepArgs(C.Structure):      # include/adm.h: adm_sched_step_args
+    _fields_ = [
+        ("x", C.c_void_p), ("eps", C.c_void_p), ("eps_uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise", C.c_void_p),
+        ("out", C.c_void_p), ("u8_out", C.c_void_p), ("coef_table", C.c_void_p), ("k_hist_table", C.c_void_p), ("hist", C.c_void_p),
+        ("step_dev", C.c_void_p), ("step", C.c_int), ("mask", C.c_void_p), ("n_mask_steps", C.c_int), ("mask_start", C.c_int),
+        ("mask_end", C.c_int), ("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("mode", C.c_int), ("prediction", C.c_int),
+        ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float), ("max_value", C.c_float), ("scale", C.c_void_p), ("noise_source", C.c_int),
+        ("seed", C.c_uint64), ("row_offset", C.c_int),
+    ]
+
+
+class SampleLoopArgs(C.Structure):     # include/adm.h: adm_sample_loop_args
+    _fields_ = [
+        ("x", C.c_void_p), ("B", C.c_int), ("coef_host", C.POINTER(SchedCoef)), ("k_hist_host", c_float_p), ("n_steps", C.c_int),
+        ("step_noise", C.c_void_p), ("mask", C.c_void_p), ("mask_start", C.c_int), ("mask_end", C.c_int), ("u8_out", C.c_void_p),
+        ("use_graph", C.c_int), ("mode", C.c_int), ("prediction", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float),
+        ("max_value", C.c_float), ("encoding_uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise_source", C.c_int),
+        ("seed", C.c_uint64), ("row_offset", C.c_int),
+    ]
+
+
+SCHED_PLAIN, SCHED_THRESH, SCHED_MULTISTEP = 0, 1, 2   # the structs' `mode`
+
+
 class WgradVariant(C.Structure):       # include/adm.h: adm_wgrad_variant
     _fields_ = [("kernel", C.c_int), ("reduce", C.c_int), ("split", C.c_int), ("tiles_per_block", C.c_int)]
 
@@ -102,6 +126,8 @@ _SIGS = {
     "adm_randn": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "adm_sched_step_philox": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_int] * 7 +
                               [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint64, C.c_int]),
+    "adm_sched_step_ex": (C.c_int, [C.POINTER(SchedStepArgs), C.c_void_p]),
+    "adm_sched_threshold_ex": (C.c_int, [C.POINTER(SchedStepArgs), C.c_void_p]),
     "adm_noise_and_velocity": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_long, C.c_void_p]),
     "adm_add_noise": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                 C.c_int, C.c_int, C.c_long, C.c_void_p]),
@@ -164,6 +190,7 @@ _SIGS = {
     "adm_sample_loop_philox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                          C.c_void_p, C.c_float, C.c_uint64, C.c_int]),
+    "adm_sample_loop_ex": (C.c_int, [C.c_void_p, C.POINTER(SampleLoopArgs), C.c_void_p]),
     "adm_encode_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_int, C.c_void_p]),
 }
 # entry points added by later translation units (k_mel.hip); bound when present in the header AND the library
@@ -221,6 +248,7 @@ _OPTIONAL_SIGS = {
 
 _lib = None
 _lib_path = None
+_device_build = False
 
 
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int)   # include/adm.h: adm_bucket_fn
@@ -247,7 +275,8 @@ def load(path=None):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    _lib, _lib_path = lib, path
+    global _device_build
+    _lib, _lib_path, _device_build = lib, path, bool(lib.adm_is_device_build())
     return lib
 
 
@@ -256,7 +285,9 @@ def lib():
 
 
 def is_device_build():
-    return bool(lib().adm_is_device_build())
+    """Asked once per loaded library: `ptr` consults it for every pointer of every call."""
+    lib()
+    return _device_build
 
 
 def default_device():

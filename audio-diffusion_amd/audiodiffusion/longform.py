@@ -7,7 +7,7 @@ heavy parts are batched on the device:
                      whole grid of weights (`ops.slerp_grid`, one launch pair), ONE batched sampling of all of them.
 * `outpaint`       — cell 16: extend a clip segment by segment; every new segment is generated with its first
                      `overlap_secs` pinned to the tail of the previous one (`mask_start_secs`): the per-step mask overwrite
-                     is part of the captured denoising graph (csrc/k_sched.hip `sched_step_kernel<MODE>`, every mode), not a Python loop.
+                     is part of the captured denoising graph (csrc/k_sched.hip `sched_step_kernel`, every instantiation), not a Python loop.
 * `remix_track`    — cell 20: re-generate a whole track in overlapping slices from `start_step`, re-inserting (peak-
                      normalised) the tail of what was generated into the head of the next slice.
 

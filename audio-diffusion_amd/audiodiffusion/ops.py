@@ -65,117 +65,75 @@ def randn(shape, seed, row_offset=0, t=0, noise_stream=0, device=None):
     return out
 
 
+def _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out=None, u8_out=None, noise=None, mask=None,
+                mask_start=0, mask_end=0):
+    """The `adm_sched_step_args` (include/adm.h) of a plain step on x, eps: (B,C,H,W); the callers add their mode's fields."""
+    _f32(x), _f32(eps)
+    B, Cc, H, W = x.shape
+    a = N.SchedStepArgs(x=N.ptr(x), eps=N.ptr(eps), noise=N.ptr(noise), out=N.ptr(out), u8_out=N.ptr(u8_out), coef_table=N.ptr(coef_table),
+                        step_dev=N.ptr(step_dev), step=int(step), mask=N.ptr(mask), n_mask_steps=mask.shape[1] if mask is not None else 0,
+                        mask_start=int(mask_start), mask_end=int(mask_end), B=B, C=Cc, H=H, W=W, prediction=int(prediction))
+    if _guidance(eps, uncond, guidance_scale):
+        a.eps_uncond, a.guidance_scale = N.ptr(uncond), float(guidance_scale)
+    return a
+
+
+def _set_threshold(a, ratio, max_value, scale):
+    """The selection's fields of `a`: the ranks of `ratio` over one sample, the maximum and the (B,) tensor that receives the thresholds."""
+    a.lo, a.hi, a.w = threshold_ranks(a.C * a.H * a.W, ratio)
+    a.max_value, a.scale = float(max_value), N.ptr(scale)
+
+
 def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None, prediction=0, uncond=None,
                     guidance_scale=None):
     """Per-sample dynamic threshold s_b = clamp(quantile(|x0_b|, ratio), 1, max_value) of x0 = (x - sqrt_beta*eps) / sqrt_alpha
     (csrc/k_sched.hip `sched_threshold_kernel`: an exact radix select on the device, equal to torch.quantile to the bit). -> (B,) fp32.
-    prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model and x0 is formed accordingly
-    (`adm_sched_threshold_pred`). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional output and x0 is that of
-    o = uncond + guidance_scale * (eps - uncond) (`adm_sched_threshold_guided`)."""
-    _f32(x), _f32(eps)
-    B, Cc, H, W = x.shape
-    lo, hi, w = threshold_ranks(Cc * H * W, ratio)
-    out = torch.empty((B,), dtype=torch.float32, device=x.device) if out is None else out
-    if _guidance(eps, uncond, guidance_scale):
-        N.check(N.lib().adm_sched_threshold_guided(N.ptr(x), N.ptr(eps), N.ptr(uncond), float(guidance_scale), N.ptr(coef_table),
-                                                   N.ptr(step_dev), int(step), lo, hi, w, float(max_value), N.ptr(out), B, Cc, H, W,
-                                                   N.stream_for(x), int(prediction)))
-        return out
-    if prediction != 0:
-        N.check(N.lib().adm_sched_threshold_pred(N.ptr(x), N.ptr(eps), N.ptr(coef_table), N.ptr(step_dev), int(step), lo, hi, w,
-                                                 float(max_value), N.ptr(out), B, Cc, H, W, N.stream_for(x), int(prediction)))
-        return out
-    N.check(N.lib().adm_sched_threshold(N.ptr(x), N.ptr(eps), N.ptr(coef_table), N.ptr(step_dev), int(step), lo, hi, w,
-                                        float(max_value), N.ptr(out), B, Cc, H, W, N.stream_for(x)))
+    prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model and x0 is formed accordingly. uncond,
+    guidance_scale: classifier-free guidance, `eps` is the conditional output and x0 is that of
+    o = uncond + guidance_scale * (eps - uncond). One native call (`adm_sched_threshold_ex`)."""
+    a = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale)
+    out = torch.empty((a.B,), dtype=torch.float32, device=x.device) if out is None else out
+    _set_threshold(a, ratio, max_value, out)
+    N.check(N.lib().adm_sched_threshold_ex(a, N.stream_for(x)))
     return out
 
 
 def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
                step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None, noise_seed=None, noise_row_offset=0):
-    """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194). x,eps: (B,C,H,W). threshold: None, or
-    (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it instead of the static
-    clamp (`adm_sched_step_thresholded`; scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device
-    scalar that replaces `step`. prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model
-    (`adm_sched_step_pred`; include/adm.h has the table). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional
-    model output and the step uses o = uncond + guidance_scale * (eps - uncond), combined inside the kernel (`adm_sched_step_guided`).
-    noise_seed (instead of `noise`): a row with k_noise != 0 draws its noise inside the kernel from "adm noise stream 1" — `randn(x.shape,
-    noise_seed, noise_row_offset, t=the row's timestep)` without the tensor (`adm_sched_step_philox`); noise_row_offset is the global row
-    of x[0]."""
-    _f32(x), _f32(eps)
-    B, Cc, H, W = x.shape
+    """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194), one native call (`adm_sched_step_ex`). x,eps: (B,C,H,W).
+    threshold: None, or (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it
+    instead of the static clamp (scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device scalar
+    that replaces `step`. prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model (include/adm.h has the
+    table). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional model output and the step uses
+    o = uncond + guidance_scale * (eps - uncond), combined inside the kernel. noise_seed (instead of `noise`): a row with k_noise != 0
+    draws its noise inside the kernel from "adm noise stream 1" — `randn(x.shape, noise_seed, noise_row_offset, t=the row's timestep)`
+    without the tensor; noise_row_offset is the global row of x[0]."""
     if noise_seed is not None and noise is not None:
         raise ValueError("`noise_seed` (noise drawn inside the kernel) and `noise=` (a noise tensor) exclude each other")
     out = torch.empty_like(x) if out is None else out
-    n_mask = mask.shape[1] if mask is not None else 0
-    if noise_seed is not None:
-        guided = _guidance(eps, uncond, guidance_scale)
-        lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
-        if threshold is not None:
-            lo, hi, w = threshold_ranks(Cc * H * W, threshold[0])
-            max_value = threshold[1]
-            scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
-        N.check(N.lib().adm_sched_step_philox(N.ptr(x), N.ptr(eps), N.ptr(uncond) if guided else None,
-                                              float(guidance_scale) if guided else 1.0, N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
-                                              N.ptr(step_dev), int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
-                                              N.stream_for(x), lo, hi, w, float(max_value), N.ptr(scale), int(prediction),
-                                              _seed64(noise_seed, "noise_seed"), int(noise_row_offset)))
-        return out
-    if _guidance(eps, uncond, guidance_scale):
-        lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
-        if threshold is not None:
-            lo, hi, w = threshold_ranks(Cc * H * W, threshold[0])
-            max_value = threshold[1]
-            scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
-        N.check(N.lib().adm_sched_step_guided(N.ptr(x), N.ptr(eps), N.ptr(uncond), float(guidance_scale), N.ptr(noise), N.ptr(out),
-                                              N.ptr(u8_out), N.ptr(coef_table), None, None, N.ptr(step_dev), int(step), N.ptr(mask),
-                                              n_mask, int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x), lo, hi, w,
-                                              float(max_value), N.ptr(scale), int(prediction)))
-        return out
-    if prediction != 0:
-        lo, hi, w, max_value, scale = 0, 0, 0.0, 1.0, None
-        if threshold is not None:
-            lo, hi, w = threshold_ranks(Cc * H * W, threshold[0])
-            max_value = threshold[1]
-            scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
-        N.check(N.lib().adm_sched_step_pred(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
-                                            N.ptr(step_dev), int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H,
-                                            W, N.stream_for(x), lo, hi, w, float(max_value), N.ptr(scale), int(prediction)))
-        return out
+    a = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out, u8_out, noise, mask, mask_start, mask_end)
     if threshold is not None:
-        ratio, max_value = threshold
-        lo, hi, w = threshold_ranks(Cc * H * W, ratio)
-        scale = torch.empty((B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
-        N.check(N.lib().adm_sched_step_thresholded(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out),
-                                                   N.ptr(coef_table), N.ptr(step_dev), int(step), N.ptr(mask), n_mask,
-                                                   int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x), lo, hi, w,
-                                                   float(max_value), N.ptr(scale)))
-        return out
-    N.check(N.lib().adm_sched_step(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
-                                   N.ptr(step_dev), int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
-                                   N.stream_for(x)))
+        a.mode = N.SCHED_THRESH   # (`scale` is a local: the struct holds its address only, and it must outlive the call)
+        scale = torch.empty((a.B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+        _set_threshold(a, threshold[0], threshold[1], scale)
+    if noise_seed is not None:
+        a.noise_source, a.seed, a.row_offset = 1, _seed64(noise_seed, "noise_seed"), int(noise_row_offset)
+    N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
     return out
 
 
 def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
                     u8_out=None, step_dev=None, uncond=None, guidance_scale=None):
-    """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,) fp32
-    beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev: optional
-    int32 device scalar that replaces `step`. uncond, guidance_scale: classifier-free guidance as in sched_step; hist then holds x0 of the
-    guided output."""
-    _f32(x), _f32(eps), _f32(hist), _f32(k_hist_table)
+    """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP, ...>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,)
+    fp32 beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev:
+    optional int32 device scalar that replaces `step`. uncond, guidance_scale: classifier-free guidance as in sched_step; hist then
+    holds x0 of the guided output."""
+    _f32(hist), _f32(k_hist_table)
     assert hist.shape == x.shape and k_hist_table.numel() == coef_table.shape[0]
-    B, Cc, H, W = x.shape
     out = torch.empty_like(x) if out is None else out
-    n_mask = mask.shape[1] if mask is not None else 0
-    if _guidance(eps, uncond, guidance_scale):
-        N.check(N.lib().adm_sched_step_guided(N.ptr(x), N.ptr(eps), N.ptr(uncond), float(guidance_scale), N.ptr(noise), N.ptr(out),
-                                              N.ptr(u8_out), N.ptr(coef_table), N.ptr(k_hist_table), N.ptr(hist), N.ptr(step_dev),
-                                              int(step), N.ptr(mask), n_mask, int(mask_start), int(mask_end), B, Cc, H, W,
-                                              N.stream_for(x), 0, 0, 0.0, 1.0, None, 0))
-        return out
-    N.check(N.lib().adm_sched_multistep(N.ptr(x), N.ptr(eps), N.ptr(noise), N.ptr(out), N.ptr(u8_out), N.ptr(coef_table),
-                                        N.ptr(k_hist_table), N.ptr(hist), N.ptr(step_dev), int(step), N.ptr(mask), n_mask,
-                                        int(mask_start), int(mask_end), B, Cc, H, W, N.stream_for(x)))
+    a = _sched_args(x, eps, coef_table, step, step_dev, 0, uncond, guidance_scale, out, u8_out, noise, mask, mask_start, mask_end)
+    a.mode, a.k_hist_table, a.hist = N.SCHED_MULTISTEP, N.ptr(k_hist_table), N.ptr(hist)
+    N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
     return out
 
 

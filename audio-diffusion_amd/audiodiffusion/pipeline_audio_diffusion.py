@@ -2,7 +2,7 @@
 
 Same constructor, `__call__` signature/defaults (`:72-87`), `encode` (`:208`), `slerp` (`:244`),
 `get_default_steps` (`:63`) and return types. The denoising loop (`:159-185`), the scheduler step, the mask
-overwrite and the uint8 dequantisation (`:192-194`) run as ONE native call (`adm_sample_loop`: a captured
+overwrite and the uint8 dequantisation (`:192-194`) run as ONE native call (`adm_sample_loop_ex`: a captured
 hipGraph of {UNet forward, fused scheduler epilogue} replayed per step, csrc/unet_exec.hip); the audio codec
 runs in the Mel HIP kernels. `diffusers` is not required: a minimal `DiffusionPipeline`-compatible base
 (`from_pretrained / save_pretrained / to / device / progress_bar / register_modules`) reads and writes the
@@ -205,18 +205,18 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                  device_noise_seed=None, device_noise_row_offset=0):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
         before that step index, so that a single step of a long schedule can be compared in isolation.
+        Every combination is one `adm_sample_loop_args` (include/adm.h) and one `adm_sample_loop_ex` call per chunk.
         guidance_scale > 1: every step is two forwards (the encoding, the negative encoding) and one guided step kernel, inside the
-        same native call (`adm_sample_loop_guided`); otherwise today's entry points, one forward per step.
+        same native call; otherwise one forward per step.
         device_noise_seed: the noise of every noisy row is drawn inside the step kernel ("adm noise stream 1", include/adm.h) at (seed,
-        device_noise_row_offset + b, the row's timestep): ONE native call (`adm_sample_loop_philox`) whatever the number of steps, no
-        staging tensor, no chunks, no synchronisation. A schedule without noisy rows (DDIM with eta == 0, the multistep solver) takes
-        today's entry points."""
+        device_noise_row_offset + b, the row's timestep): ONE native call whatever the number of steps, no staging tensor, no chunks,
+        no synchronisation. A schedule without noisy rows (DDIM with eta == 0, the multistep solver) has nothing to draw."""
         sched, unet = self.scheduler, self.unet
         self._device_noise(device_noise_seed, step_generator=step_generator, step_noise=step_noise)
         guided = self._guided(guidance_scale, negative_encoding, encoding)
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
         thresh = None if multistep else sched.threshold()
-        pred = 0 if multistep else sched.prediction   # 0 epsilon: today's three entry points; otherwise adm_sample_loop_pred
+        pred = 0 if multistep else sched.prediction   # the C-ABI's `prediction`; the multistep step is epsilon only
         # (a multistep run that starts late starts first order: its rows depend on where it starts, not only on the slice)
         rows = sched.loop_rows(start_step, stop_step) if multistep else sched.coef_rows(eta)[start_step:stop_step]
         n = len(rows)
@@ -263,41 +263,22 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 mask_chunk = mask[:, done:done + m].contiguous()
                 mask_ptr = N.ptr(mask_chunk)
             u8_ptr = N.ptr(u8) if (last and u8 is not None) else None
-            if philox:   # noise drawn in the step kernel: plain / thresholded, any prediction type, guided or not, all steps at once
-                assert m == n and not multistep
-                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
-                N.check(N.lib().adm_sample_loop_philox(h, N.ptr(x), B, coef, m, mask_ptr, int(mask_start), int(mask_end), u8_ptr,
-                                                       int(use_graph), N.stream_for(x), lo, hi, w,
-                                                       thresh[1] if thresh is not None else 1.0, int(thresh is not None), pred,
-                                                       N.ptr(unet._enc_uncond) if guided else None,
-                                                       float(guidance_scale) if guided else 1.0,
-                                                       ops._seed64(device_noise_seed, "device_noise_seed"), int(device_noise_row_offset)))
-            elif guided:   # every mode through the one guided entry point; the multistep loop stays one call
-                assert not multistep or m == n
-                khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub]) if multistep else None
-                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
-                N.check(N.lib().adm_sample_loop_guided(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
-                                                       int(mask_end), u8_ptr, int(use_graph), N.stream_for(x), lo, hi, w,
-                                                       thresh[1] if thresh is not None else 1.0, int(thresh is not None), pred,
-                                                       N.ptr(unet._enc_uncond), float(guidance_scale)))
-            elif multistep:   # no noise, so no chunking: the history of the previous x0 lives inside this one native call
-                assert m == n
-                khist = (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
-                N.check(N.lib().adm_sample_loop_multistep(h, N.ptr(x), B, coef, khist, m, noise_ptr, mask_ptr, int(mask_start),
-                                                          int(mask_end), u8_ptr, int(use_graph), N.stream_for(x)))
-            elif pred != 0:   # a sample / v_prediction model: the same loop with the step (and selection) kernel of that type
-                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0]) if thresh is not None else (0, 0, 0.0)
-                N.check(N.lib().adm_sample_loop_pred(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start), int(mask_end),
-                                                     u8_ptr, int(use_graph), N.stream_for(x), lo, hi, w,
-                                                     thresh[1] if thresh is not None else 1.0, int(thresh is not None), pred))
+            # one entry point for every combination; device noise and the multistep history both need all steps in this one call
+            assert m == n or not (philox or multistep)
+            args = N.SampleLoopArgs(x=N.ptr(x), B=B, coef_host=coef, n_steps=m, step_noise=noise_ptr, mask=mask_ptr,
+                                    mask_start=int(mask_start), mask_end=int(mask_end), u8_out=u8_ptr, use_graph=int(use_graph),
+                                    prediction=pred, max_value=1.0, guidance_scale=1.0)
+            if multistep:
+                args.mode, args.k_hist_host = N.SCHED_MULTISTEP, (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
             elif thresh is not None:   # dynamic thresholding: the statistic is over this tensor's C*H*W (the latent's, with a VAE)
-                lo, hi, w = ops.threshold_ranks(Cc * H * W, thresh[0])
-                N.check(N.lib().adm_sample_loop_thresholded(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start),
-                                                            int(mask_end), u8_ptr, int(use_graph), N.stream_for(x), lo, hi, w,
-                                                            thresh[1]))
-            else:
-                N.check(N.lib().adm_sample_loop(h, N.ptr(x), B, coef, m, noise_ptr, mask_ptr, int(mask_start), int(mask_end),
-                                                u8_ptr, int(use_graph), N.stream_for(x)))
+                args.mode, args.max_value = N.SCHED_THRESH, thresh[1]
+                args.lo, args.hi, args.w = ops.threshold_ranks(Cc * H * W, thresh[0])
+            if guided:   # two forwards per step, the second on this encoding
+                args.encoding_uncond, args.guidance_scale = N.ptr(unet._enc_uncond), float(guidance_scale)
+            if philox:   # noise drawn in the step kernel: no staging tensor
+                args.noise_source, args.row_offset = 1, int(device_noise_row_offset)
+                args.seed = ops._seed64(device_noise_seed, "device_noise_seed")
+            N.check(N.lib().adm_sample_loop_ex(h, args, N.stream_for(x)))
             if x.is_cuda and (noise_ptr is not None or mask_ptr is not None) and not last:
                 torch.cuda.current_stream(x.device).synchronize()  # staging buffers are rewritten next chunk
             done += m

@@ -3,25 +3,25 @@
 Reference call sites: `audiodiffusion/pipeline_audio_diffusion.py:115,150,157,166-179,221-234`,
 `scripts/train_unet.py:161-164,250`. Host side (this file): the beta/alpha tables and the per-step scalar
 coefficients, computed in the same 0-d fp32 tensor arithmetic diffusers==0.24.0 uses. Device side: ONE fused
-HIP kernel per step (`adm_sched_step`, csrc/k_sched.hip) instead of ~12 eager elementwise kernels plus D2H
+HIP kernel per step (`adm_sched_step_ex`, csrc/k_sched.hip) instead of ~12 eager elementwise kernels plus D2H
 scalar reads. `coef_rows()` exports the whole coefficient table so the native sampling loop
-(`adm_sample_loop`) can replay a captured hipGraph for every step. `DPMSolverMultistepScheduler` (second-order multistep,
-not used by the reference itself) goes through the sibling kernel and loop (`adm_sched_multistep`,
-`adm_sample_loop_multistep`): one more coefficient per step and a per-element history of the previous x0 prediction.
+(`adm_sample_loop_ex`) can replay a captured hipGraph for every step. `DPMSolverMultistepScheduler` (second-order multistep,
+not used by the reference itself) goes through the same two entry points with `mode` 2 (the multistep instantiation of the
+kernel): one more coefficient per step and a per-element history of the previous x0 prediction.
 `thresholding=True` (DDPM / DDIM) replaces the static clamp of x0 by the dynamic one: a per-sample percentile selected on the
-device (`adm_sched_threshold`) in front of the step kernel, in `step()` and inside the captured loop (`adm_sample_loop_thresholded`).
+device (`sched_threshold_kernel`) in front of the step kernel, in `step()` and inside the captured loop (`mode` 1).
 `prediction_type` "sample" / "v_prediction" (DDPM / DDIM): the model output is the clean sample or the velocity sa*eps - sb*x0 instead
 of the noise. The coefficient rows do not change; the step and selection kernels turn (x, output) into (x0, eps) by the type
-(`adm_sched_step_pred`, `adm_sched_threshold_pred`, `adm_sample_loop_pred`; the table is in include/adm.h), and `get_velocity` /
+(the structs' `prediction`; the table is in include/adm.h), and `get_velocity` /
 `ops.noise_and_velocity` give the training target. With them come `timestep_spacing` "linspace" / "trailing" and
 `rescale_betas_zero_snr` (Lin et al. 2023), whose last training timestep has alphas_cumprod == 0: only the two new types can start
 there, an epsilon scheduler refuses such a schedule. The multistep scheduler stays epsilon-only.
 Classifier-free guidance: `step(..., model_output_uncond=u, guidance_scale=g)` of the three schedulers takes the conditional output as
-`model_output` and steps with u + g*(model_output - u), combined inside the one fused kernel (`adm_sched_step_guided`; the
+`model_output` and steps with u + g*(model_output - u), combined inside the one fused kernel (the struct's `eps_uncond`; the
 thresholded and the multistep paths included). Both keywords or neither; the `<= 1 means off` rule belongs to the pipeline.
 Device noise: `step(..., device_noise_seed=s, device_noise_row_offset=r)` (DDPM, DDIM with eta > 0) draws the step's noise inside the fused
 kernel from "adm noise stream 1" (include/adm.h) at (seed s, global row r + b, the step's timestep) instead of `randn_tensor`
-(`adm_sched_step_philox`). Not together with `generator` or `variance_noise`.
+(the struct's `noise_source` 1). Not together with `generator` or `variance_noise`.
 """
 import json
 import math
@@ -373,13 +373,13 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
 
     The update is linear in (x, x0 of this step, x0 of the previous step):
         x' = k_x*x + k_x0*m0 + k_hist*m1,   m0 = (x - sqrt_beta*eps) / sqrt_alpha
-    so a step is one fused kernel (`adm_sched_multistep`) with the eight `adm_sched_coef` fields, one extra per-step
+    so a step is one fused kernel (`adm_sched_step_ex`, `mode` 2) with the eight `adm_sched_coef` fields, one extra per-step
     coefficient `k_hist` and a per-element history buffer. Scalars are computed in float64 on the host and rounded to fp32
     once. Built: `solver_order` 1 and 2, `algorithm_type="dpmsolver++"`, `solver_type` midpoint / heun, the three timestep
     spacings, `final_sigmas_type` zero / sigma_min, `lower_order_final`, `euler_at_final`. Everything else raises
     NotImplementedError naming the key (the SDE variants need per-step noise and a history that survives the pipeline's
     noise-staging chunks). `thresholding=True` raises as well: the selection kernel of the DDIM / DDPM schedulers
-    (`adm_sched_threshold`) is what a thresholded multistep step would reuse: one more instantiation of `sched_step_kernel`, which is not built."""
+    (`sched_threshold_kernel`) is what a thresholded multistep step would reuse: one more instantiation of `sched_step_kernel`, which is not built."""
     _class_name = "DPMSolverMultistepScheduler"
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
                      solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,

@@ -6,8 +6,10 @@
 namespace adm {
 
 // k_sched.hip
-enum { SCHED_PLAIN = 0, SCHED_THRESH = 1, SCHED_MULTISTEP = 2 };   // which sched_step_kernel<MODE> runs
-enum { PRED_EPSILON = 0, PRED_SAMPLE = 1, PRED_V = 2 };            // what the model output is (the C-ABI's `prediction`); not 0: sched_step_pred_kernel<MODE, PRED>
+// the four template parameters of sched_step_kernel<MODE, PRED, GUIDED, PHILOX>: MODE and PRED are these, GUIDED is p.eps_uncond != nullptr and
+// PHILOX is p.philox != 0. launch_sched_step looks the kernel up by the four; the C-ABI's `mode` and `prediction` carry the same values.
+enum { SCHED_PLAIN = 0, SCHED_THRESH = 1, SCHED_MULTISTEP = 2 };   // how x0 is clamped and what the update adds
+enum { PRED_EPSILON = 0, PRED_SAMPLE = 1, PRED_V = 2 };            // what the model output is
 struct SchedStepParams {   // the step kernel's parameter block; the caller fills the first three lines and its mode's extras
   const float* x; const float* eps; const float* noise; float* out; uint8_t* u8; const adm_sched_coef* table;
   const int* step_dev; int step; const float* mask; int n_mask_steps, mask_start, mask_end, B, C, H, W;
@@ -23,9 +25,7 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
 int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, hipStream_t st);
 int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
 int launch_step_advance(int* step_dev, hipStream_t st);
-int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
-                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st,
-                           int pred = PRED_EPSILON, const float* eps_uncond = nullptr, float guidance = 1.f);
+int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred = PRED_EPSILON);   // the selection alone: p.scale[b] = s_b
 int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 113; }   // 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 114; }   // 114: adm_sched_step_args / adm_sample_loop_args and adm_sched_step_ex / adm_sched_threshold_ex / adm_sample_loop_ex (one struct-argument entry point per family; the positional ones are frozen); 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -100,84 +100,135 @@ int adm_is_device_build(void) {
 #endif
 }
 
+// The scheduler step and the selection: all validation that is not about the shape (k_sched.hip's launchers have that) is here.
+int adm_sched_step_ex(const adm_sched_step_args* a, void* stream) {
+  ADM_REQUIRE(a != nullptr, "sched_step: null argument struct");
+  ADM_REQUIRE(a->x && a->eps && a->out && a->coef_table, "sched_step: null argument");
+  ADM_REQUIRE(a->noise_source == 0 || a->noise_source == 1, "sched_step: noise_source must be 0 (the noise buffer, or none) or 1 (adm noise stream 1)");
+  SchedStepParams p{a->x, a->eps, a->noise, a->out, a->u8_out, a->coef_table, a->step_dev, a->step, a->mask, a->n_mask_steps,
+                    a->mask_start, a->mask_end, a->B, a->C, a->H, a->W};
+  p.eps_uncond = a->eps_uncond; p.guidance = a->guidance_scale;
+  if (a->mode == SCHED_THRESH) {
+    ADM_REQUIRE(a->scale != nullptr, "sched_step: the thresholded step needs scale");
+    p.lo = a->lo; p.hi = a->hi; p.w = a->w; p.max_value = a->max_value; p.scale = a->scale;
+  }
+  if (a->mode == SCHED_MULTISTEP) {
+    ADM_REQUIRE(a->k_hist_table && a->hist, "sched_step: the multistep step needs k_hist_table and hist");
+    ADM_REQUIRE(a->scale == nullptr, "sched_step: the multistep step is epsilon only and not thresholded");
+    p.hist = a->hist; p.k_hist_table = a->k_hist_table;
+  }
+  if (a->noise_source == 1) {
+    ADM_REQUIRE(a->B > 0 && a->C > 0 && a->H > 0 && a->W > 0, "sched_step: bad shape");
+    ADM_REQUIRE(a->row_offset >= 0, "sched_step: row_offset must be >= 0");
+    ADM_REQUIRE((uint64_t)a->row_offset + (uint64_t)a->B <= 0xffffffffull, "sched_step: row_offset + B must fit in 32 bits");
+    p.philox = 1;
+    p.nvals[0] = (uint32_t)(a->seed & 0xffffffffull); p.nvals[1] = (uint32_t)(a->seed >> 32); p.nvals[2] = (uint32_t)a->row_offset; p.nvals[3] = 0;
+  }
+  return launch_sched_step(p, a->mode, (hipStream_t)stream, a->prediction);
+}
+
+int adm_sched_threshold_ex(const adm_sched_step_args* a, void* stream) {
+  ADM_REQUIRE(a != nullptr, "sched_threshold: null argument struct");
+  ADM_REQUIRE(a->x && a->eps && a->coef_table && a->scale, "sched_threshold: null argument");
+  SchedStepParams p{a->x, a->eps, nullptr, nullptr, nullptr, a->coef_table, a->step_dev, a->step, nullptr, 0, 0, 0, a->B, a->C, a->H, a->W};
+  p.eps_uncond = a->eps_uncond; p.guidance = a->guidance_scale;
+  p.lo = a->lo; p.hi = a->hi; p.w = a->w; p.max_value = a->max_value; p.scale = a->scale;
+  return launch_sched_threshold(p, (hipStream_t)stream, a->prediction);
+}
+
+// ---- the frozen positional entry points (include/adm.h): a struct fill and one call each
+static adm_sched_step_args sched_args(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
+                                      const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask, int n_mask_steps,
+                                      int mask_start, int mask_end, int B, int C, int H, int W) {
+  adm_sched_step_args a{};
+  a.x = x; a.eps = eps; a.noise = noise; a.out = out; a.u8_out = u8_out; a.coef_table = coef_table; a.step_dev = step_dev; a.step = step;
+  a.mask = mask; a.n_mask_steps = n_mask_steps; a.mask_start = mask_start; a.mask_end = mask_end; a.B = B; a.C = C; a.H = H; a.W = W;
+  return a;
+}
+// scale == NULL: the static clip (mode 0; lo, hi, w, max_value are ignored); otherwise the thresholded step
+static void sched_args_threshold(adm_sched_step_args& a, int lo, int hi, float w, float max_value, float* scale) {
+  if (scale == nullptr) return;
+  a.mode = SCHED_THRESH; a.lo = lo; a.hi = hi; a.w = w; a.max_value = max_value; a.scale = scale;
+}
+static adm_sched_step_args threshold_args(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step,
+                                          int lo, int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W) {
+  adm_sched_step_args a = sched_args(x, eps, nullptr, nullptr, nullptr, coef_table, step_dev, step, nullptr, 0, 0, 0, B, C, H, W);
+  a.lo = lo; a.hi = hi; a.w = w; a.max_value = max_value; a.scale = scale_out;
+  return a;
+}
+
 int adm_sched_step(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
                    const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask,
                    int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, void* stream) {
-  ADM_REQUIRE(x && eps && out && coef_table, "sched_step: null argument");
-  const SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
-  return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream);
+  const adm_sched_step_args a = sched_args(x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W);
+  return adm_sched_step_ex(&a, stream);
 }
 
 int adm_sched_multistep(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
                         const adm_sched_coef* coef_table, const float* k_hist_table, float* hist, const int* step_dev,
                         int step, const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C, int H,
                         int W, void* stream) {
-  ADM_REQUIRE(x && eps && out && coef_table && k_hist_table && hist, "sched_multistep: null argument");
-  SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
-  p.hist = hist; p.k_hist_table = k_hist_table;
-  return launch_sched_step(p, SCHED_MULTISTEP, (hipStream_t)stream);
+  adm_sched_step_args a = sched_args(x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W);
+  a.mode = SCHED_MULTISTEP; a.k_hist_table = k_hist_table; a.hist = hist;
+  return adm_sched_step_ex(&a, stream);
 }
 
 int adm_sched_threshold(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step, int lo,
                         int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W, void* stream) {
-  ADM_REQUIRE(x && eps && coef_table && scale_out, "sched_threshold: null argument");
-  return launch_sched_threshold(x, eps, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W,
-                                (hipStream_t)stream);
+  const adm_sched_step_args a = threshold_args(x, eps, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W);
+  return adm_sched_threshold_ex(&a, stream);
 }
 
 int adm_sched_step_thresholded(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
                                const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask,
                                int n_mask_steps, int mask_start, int mask_end, int B, int C, int H, int W, void* stream, int lo,
                                int hi, float w, float max_value, float* scale) {
-  ADM_REQUIRE(x && eps && out && coef_table && scale, "sched_step_thresholded: null argument");
-  SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
-  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
-  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream);
+  adm_sched_step_args a = sched_args(x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W);
+  a.mode = SCHED_THRESH;   // (not sched_args_threshold: a null scale is refused here, not read as "the static clip")
+  a.lo = lo; a.hi = hi; a.w = w; a.max_value = max_value; a.scale = scale;
+  return adm_sched_step_ex(&a, stream);
 }
 
 int adm_sched_threshold_pred(const float* x, const float* eps, const adm_sched_coef* coef_table, const int* step_dev, int step, int lo,
                              int hi, float w, float max_value, float* scale_out, int B, int C, int H, int W, void* stream,
                              int prediction) {
-  ADM_REQUIRE(x && eps && coef_table && scale_out, "sched_threshold_pred: null argument");
-  return launch_sched_threshold(x, eps, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W,
-                                (hipStream_t)stream, prediction);
+  adm_sched_step_args a = threshold_args(x, eps, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W);
+  a.prediction = prediction;
+  return adm_sched_threshold_ex(&a, stream);
 }
 
 int adm_sched_step_pred(const float* x, const float* eps, const float* noise, float* out, uint8_t* u8_out,
                         const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask, int n_mask_steps,
                         int mask_start, int mask_end, int B, int C, int H, int W, void* stream, int lo, int hi, float w,
                         float max_value, float* scale, int prediction) {
-  ADM_REQUIRE(x && eps && out && coef_table, "sched_step_pred: null argument");
-  SchedStepParams p{x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
-  if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
-  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
-  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);
+  adm_sched_step_args a = sched_args(x, eps, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W);
+  sched_args_threshold(a, lo, hi, w, max_value, scale);
+  a.prediction = prediction;
+  return adm_sched_step_ex(&a, stream);
 }
 
 int adm_sched_threshold_guided(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale,
                                const adm_sched_coef* coef_table, const int* step_dev, int step, int lo, int hi, float w, float max_value,
                                float* scale_out, int B, int C, int H, int W, void* stream, int prediction) {
-  ADM_REQUIRE(x && eps_cond && eps_uncond && coef_table && scale_out, "sched_threshold_guided: null argument");
-  return launch_sched_threshold(x, eps_cond, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W,
-                                (hipStream_t)stream, prediction, eps_uncond, guidance_scale);
+  ADM_REQUIRE(eps_uncond != nullptr, "sched_threshold_guided: null argument");   // (NULL means "unguided" to the struct)
+  adm_sched_step_args a = threshold_args(x, eps_cond, coef_table, step_dev, step, lo, hi, w, max_value, scale_out, B, C, H, W);
+  a.prediction = prediction; a.eps_uncond = eps_uncond; a.guidance_scale = guidance_scale;
+  return adm_sched_threshold_ex(&a, stream);
 }
 
 int adm_sched_step_guided(const float* x, const float* eps_cond, const float* eps_uncond, float guidance_scale, const float* noise,
                           float* out, uint8_t* u8_out, const adm_sched_coef* coef_table, const float* k_hist_table, float* hist,
                           const int* step_dev, int step, const float* mask, int n_mask_steps, int mask_start, int mask_end, int B, int C,
                           int H, int W, void* stream, int lo, int hi, float w, float max_value, float* scale, int prediction) {
-  ADM_REQUIRE(x && eps_cond && eps_uncond && out && coef_table, "sched_step_guided: null argument");
-  SchedStepParams p{x, eps_cond, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
-  p.eps_uncond = eps_uncond; p.guidance = guidance_scale;
-  if (hist != nullptr) {
-    ADM_REQUIRE(k_hist_table != nullptr, "sched_step_guided: the multistep step needs k_hist_table");
-    ADM_REQUIRE(prediction == PRED_EPSILON && scale == nullptr, "sched_step_guided: the multistep step is epsilon only and not thresholded");
-    p.hist = hist; p.k_hist_table = k_hist_table;
-    return launch_sched_step(p, SCHED_MULTISTEP, (hipStream_t)stream);
+  ADM_REQUIRE(eps_uncond != nullptr, "sched_step_guided: null argument");   // (NULL means "unguided" to the struct)
+  adm_sched_step_args a = sched_args(x, eps_cond, noise, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W);
+  a.eps_uncond = eps_uncond; a.guidance_scale = guidance_scale; a.prediction = prediction;
+  if (hist != nullptr) {   // the multistep step; with a scale as well it is refused as "not thresholded"
+    a.mode = SCHED_MULTISTEP; a.k_hist_table = k_hist_table; a.hist = hist; a.scale = scale;
+  } else {
+    sched_args_threshold(a, lo, hi, w, max_value, scale);
   }
-  if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
-  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
-  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);
+  return adm_sched_step_ex(&a, stream);
 }
 
 int adm_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, void* stream) {
@@ -188,17 +239,11 @@ int adm_sched_step_philox(const float* x, const float* eps_cond, const float* ep
                           const adm_sched_coef* coef_table, const int* step_dev, int step, const float* mask, int n_mask_steps,
                           int mask_start, int mask_end, int B, int C, int H, int W, void* stream, int lo, int hi, float w, float max_value,
                           float* scale, int prediction, uint64_t seed, int row_offset) {
-  ADM_REQUIRE(x && eps_cond && out && coef_table, "sched_step_philox: null argument");
-  ADM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "sched_step_philox: bad shape");
-  ADM_REQUIRE(row_offset >= 0, "sched_step_philox: row_offset must be >= 0");
-  ADM_REQUIRE((uint64_t)row_offset + (uint64_t)B <= 0xffffffffull, "sched_step_philox: row_offset + B must fit in 32 bits");
-  SchedStepParams p{x, eps_cond, nullptr, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W};
-  p.eps_uncond = eps_uncond; p.guidance = guidance_scale;
-  p.philox = 1;
-  p.nvals[0] = (uint32_t)(seed & 0xffffffffull); p.nvals[1] = (uint32_t)(seed >> 32); p.nvals[2] = (uint32_t)row_offset; p.nvals[3] = 0;
-  if (scale == nullptr) return launch_sched_step(p, SCHED_PLAIN, (hipStream_t)stream, prediction);
-  p.lo = lo; p.hi = hi; p.w = w; p.max_value = max_value; p.scale = scale;
-  return launch_sched_step(p, SCHED_THRESH, (hipStream_t)stream, prediction);
+  adm_sched_step_args a = sched_args(x, eps_cond, nullptr, out, u8_out, coef_table, step_dev, step, mask, n_mask_steps, mask_start, mask_end, B, C, H, W);
+  a.eps_uncond = eps_uncond; a.guidance_scale = guidance_scale; a.prediction = prediction;
+  sched_args_threshold(a, lo, hi, w, max_value, scale);
+  a.noise_source = 1; a.seed = seed; a.row_offset = row_offset;
+  return adm_sched_step_ex(&a, stream);
 }
 
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

@@ -3,37 +3,38 @@
 // (reference: audiodiffusion/pipeline_audio_diffusion.py:165-185,192-194; SURVEY.md §8(a) S2-S4,P4,P5).
 // One float4 per lane per iteration, grid-stride; algorithmic bytes: 12 B/elem (x, eps in; out), +4 with a noise BUFFER, +0 with noise
 // drawn in the kernel (the noise stream below): a noisy step moves 12 B/elem instead of 16 (guided: 16 instead of 20).
-// sched_step_kernel<MODE> is ONE kernel for the three steps; the loop, the noise slice, the mask overwrite and the u8 pack are shared and only
-// the handful of lines that compute x0 and the update depend on MODE:
-//   SCHED_PLAIN      DDIM / DDPM with the row's static clamp.
-//   SCHED_MULTISTEP  the second-order multistep solver (DPM-Solver++ 2M): the update is linear in (x, x0 of this step, x0 of the previous
-//                    step), so it adds one per-step coefficient k_hist and one per-element history buffer that the same lane reads and
-//                    rewrites in place: +8 B/elem over SCHED_PLAIN (one history read, one history write), 20 B/elem in all.
-//   SCHED_THRESH     sched_threshold_kernel first: dynamic thresholding (Imagen §2.3) of x0 in place of the static clamp. The per-sample
-//                    percentile of |x0| is an exact order statistic: one workgroup per sample, MSB-first radix select (11 + 10 + 10 bits)
-//                    over an LDS histogram of the bit pattern of |x0|; x0 is recomputed from x and eps in every pass (8 B/elem per pass,
-//                    3 passes + 1 when the two ranks straddle two distinct values: 24-32 B/elem, L2-resident), nothing but the B scales
-//                    goes to global memory.
-// What the model predicts (PRED_EPSILON / PRED_SAMPLE / PRED_V) is a second template parameter of the SAME step body and of the selection's
-// key: sched_step_kernel<MODE> and sched_threshold_kernel are the epsilon instantiations under their old names, sched_step_pred_kernel
-// <MODE, PRED> and sched_threshold_pred_kernel<PRED> the sample / v_prediction ones (SCHED_PLAIN and SCHED_THRESH; the multistep step is
-// epsilon only). Same traffic: the parameterisation only changes the few flops that turn (x, model output) into (x0, eps).
-// Classifier-free guidance (GUIDED, the third template parameter of the same body and of the selection's key): p.eps is the conditional
-// model output c, p.eps_uncond the unconditional one u, and o = sched_guided(u, c, g) stands wherever the model output stood. One more
-// float4 load per lane: 16 B/elem where the unguided step moves 12 (+4 with noise, +8 with the multistep history, as before); every pass of
-// the selection reads 12 B/elem instead of 8. sched_step_guided_kernel<MODE, PRED> / sched_threshold_guided_kernel<PRED>: plain and
-// thresholded for the three prediction types, multistep for epsilon. The unguided kernels keep their names and their arithmetic.
-// Noise has three sources: none, a buffer (p.noise), and "adm noise stream 1" (include/adm.h): Philox4x32-10 keyed by the seed and counted
-// by (float4 index inside the sample, global sample row, timestep, stream id), turned into four normals by two Box-Muller pairs, drawn by
-// the lane that consumes them. noise_stream_normals is the ONE helper for randn_fill_kernel (the initial latent, and what tests
-// materialise) and for the step body. The source is a TEMPLATE parameter (PHILOX, the fourth of sched_step_body), not a runtime branch:
-// the 14 instantiations that existed before it (3 sched_step_kernel, 4 sched_step_pred_kernel, 7 sched_step_guided_kernel) compile without
-// a line of the generator and keep their registers and their arithmetic; sched_step_philox_kernel<MODE, PRED, GUIDED> adds 12 (plain and
-// thresholded, three prediction types, guided or not; the multistep step has no noise rows): 26 step kernels in all. In the captured loop
-// the key, the row offset and the stream id are read from a 16-byte device block (p.nblock), as the step index is read from *step_dev, so a
-// new seed or shard offset replays the same graph; the eager entry point passes them by value (p.nvals).
+// ONE step kernel, sched_step_kernel<MODE, PRED, GUIDED, PHILOX>: the loop, the noise slice, the mask overwrite and the u8 pack are shared,
+// and each template parameter changes a handful of lines of sched_step_body:
+//   MODE    SCHED_PLAIN      DDIM / DDPM with the row's static clamp.
+//           SCHED_MULTISTEP  the second-order multistep solver (DPM-Solver++ 2M): the update is linear in (x, x0 of this step, x0 of the
+//                            previous step), so it adds one per-step coefficient k_hist and one per-element history buffer that the same
+//                            lane reads and rewrites in place: +8 B/elem over SCHED_PLAIN (one history read, one write), 20 B/elem in all.
+//           SCHED_THRESH     sched_threshold_kernel first: dynamic thresholding (Imagen §2.3) of x0 in place of the static clamp. The
+//                            per-sample percentile of |x0| is an exact order statistic: one workgroup per sample, MSB-first radix select
+//                            (11 + 10 + 10 bits) over an LDS histogram of the bit pattern of |x0|; x0 is recomputed from x and eps in every
+//                            pass (8 B/elem per pass, 3 passes + 1 when the two ranks straddle two distinct values: 24-32 B/elem,
+//                            L2-resident), nothing but the B scales goes to global memory.
+//   PRED    what the model predicts (PRED_EPSILON / PRED_SAMPLE / PRED_V), also a parameter of the selection's key. Same traffic: it only
+//           changes the few flops that turn (x, model output) into (x0, eps).
+//   GUIDED  classifier-free guidance, also a parameter of the selection's key: p.eps is the conditional model output c, p.eps_uncond the
+//           unconditional one u, and o = sched_guided(u, c, g) stands wherever the model output stood. One more float4 load per lane:
+//           16 B/elem where the unguided step moves 12 (+4 with a noise buffer, +8 with the multistep history); every pass of the
+//           selection reads 12 B/elem instead of 8.
+//   PHILOX  the noise source. Noise has three: none, a buffer (p.noise), and "adm noise stream 1" (include/adm.h): Philox4x32-10 keyed by
+//           the seed and counted by (float4 index inside the sample, global sample row, timestep, stream id), turned into four normals by
+//           two Box-Muller pairs, drawn by the lane that consumes them. noise_stream_normals is the ONE helper for randn_fill_kernel (the
+//           initial latent, and what tests materialise) and for the step body. A template parameter, not a runtime branch: the
+//           instantiations without it compile without a line of the generator. In the captured loop the key, the row offset and the
+//           stream id are read from a 16-byte device block (p.nblock), as the step index is read from *step_dev, so a new seed or shard
+//           offset replays the same graph; the eager entry point passes them by value (p.nvals).
+// 26 instantiations are built: plain and thresholded for the three prediction types, guided or not, with the stream or not (24), and the
+// multistep step for epsilon, guided or not (it has no noise rows). The launchers look the kernel up in a table filled at compile time
+// (kStepKernels by (mode, pred, guided, philox), kThresholdKernels by (pred, guided)); a combination that is not built is an empty slot and
+// is refused.
 #include "adm_kernels.h"
+#include <array>
 #include <cmath>
+#include <utility>
 
 namespace adm {
 
@@ -130,9 +131,8 @@ __device__ __forceinline__ unsigned pack_u8x4(float a, float b, float c, float d
 // out may alias x.
 // first, stride: the lane's first float4 and the grid's stride, which the kernel works out itself (a launch-geometry builtin is only
 // folded against the kernel's launch bounds where the kernel reads it).
-template <int MODE, int PRED, bool GUIDED, bool PHILOX = false>
+template <int MODE, int PRED, bool GUIDED, bool PHILOX>
 __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const long first, const long stride) {
-  static_assert(!PHILOX || MODE != SCHED_MULTISTEP, "the multistep step has no noise rows");
   const int s = p.step_dev ? *p.step_dev : p.step;
   const adm_sched_coef c = p.table[s];
   const float k_hist = MODE == SCHED_MULTISTEP ? p.k_hist_table[s] : 0.f;
@@ -202,26 +202,11 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
   }
 }
 
-template <int MODE>
+template <int MODE, int PRED, bool GUIDED, bool PHILOX>
 __global__ void __launch_bounds__(256) sched_step_kernel(const SchedStepParams p) {
-  sched_step_body<MODE, PRED_EPSILON, false>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-
-template <int MODE, int PRED>
-__global__ void __launch_bounds__(256) sched_step_pred_kernel(const SchedStepParams p) {
-  static_assert(MODE != SCHED_MULTISTEP && PRED != PRED_EPSILON, "the sample / v_prediction steps: plain and thresholded only");
-  sched_step_body<MODE, PRED, false>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-
-template <int MODE, int PRED>
-__global__ void __launch_bounds__(256) sched_step_guided_kernel(const SchedStepParams p) {
   static_assert(MODE != SCHED_MULTISTEP || PRED == PRED_EPSILON, "the multistep step is epsilon only");
-  sched_step_body<MODE, PRED, true>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-
-template <int MODE, int PRED, bool GUIDED>
-__global__ void __launch_bounds__(256) sched_step_philox_kernel(const SchedStepParams p) {
-  sched_step_body<MODE, PRED, GUIDED, true>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+  static_assert(MODE != SCHED_MULTISTEP || !PHILOX, "the multistep step has no noise rows");
+  sched_step_body<MODE, PRED, GUIDED, PHILOX>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 // (B, per_sample) normals of the stream at one (t, stream id): out[b][4q .. 4q+3] = noise_stream_normals(q, row_offset + b). One float4 per lane.
@@ -363,27 +348,13 @@ __device__ __forceinline__ void sched_threshold_body(
   }
 }
 
+// One signature for the six instantiations; the unguided ones ignore eps_uncond and guidance, as the body does.
+template <int PRED, bool GUIDED>
 __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
-    const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
-    const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
-    float* __restrict__ scale) {
-  sched_threshold_body<PRED_EPSILON, false>(x, eps, nullptr, 1.f, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
-}
-
-template <int PRED>
-__global__ void __launch_bounds__(kThreshThreads) sched_threshold_pred_kernel(
-    const float* __restrict__ x, const float* __restrict__ eps, const adm_sched_coef* __restrict__ table,
-    const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
-    float* __restrict__ scale) {
-  sched_threshold_body<PRED, false>(x, eps, nullptr, 1.f, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
-}
-
-template <int PRED>
-__global__ void __launch_bounds__(kThreshThreads) sched_threshold_guided_kernel(
     const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_uncond, float guidance,
     const adm_sched_coef* __restrict__ table, const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w,
     float max_value, float* __restrict__ scale) {
-  sched_threshold_body<PRED, true>(x, eps, eps_uncond, guidance, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
+  sched_threshold_body<PRED, GUIDED>(x, eps, eps_uncond, guidance, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
 }
 
 __global__ void step_advance_kernel(int* step_dev) { *step_dev += 1; }
@@ -457,39 +428,48 @@ static inline int ew_grid(long n4) {
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));  // cap + grid-stride (guide §6 G11)
 }
 
-int launch_sched_threshold(const float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step,
-                           int lo, int hi, float w, float max_value, float* scale, int B, int C, int H, int W, hipStream_t st, int pred,
-                           const float* eps_uncond, float guidance) {
-  const long per_sample = (long)C * H * W;
-  ADM_REQUIRE(B > 0 && W % 4 == 0, "sched_threshold: W must be a multiple of 4");
+// The kernel tables. A slot is a kernel's address, or nullptr for a combination that is not built: the helper keeps those from being
+// instantiated (their static_asserts would fire).
+using StepKernel = void (*)(const SchedStepParams);
+using ThresholdKernel = void (*)(const float*, const float*, const float*, float, const adm_sched_coef*, const int*, int, long, unsigned,
+                                 unsigned, float, float, float*);
+
+template <int MODE, int PRED, bool GUIDED, bool PHILOX>
+constexpr StepKernel step_kernel_or_null() {
+  if constexpr (MODE == SCHED_MULTISTEP && (PRED != PRED_EPSILON || PHILOX)) return nullptr;
+  else return sched_step_kernel<MODE, PRED, GUIDED, PHILOX>;
+}
+
+constexpr int step_slot(int mode, int pred, bool guided, bool philox) { return ((mode * 3 + pred) * 2 + guided) * 2 + philox; }
+constexpr int threshold_slot(int pred, bool guided) { return pred * 2 + guided; }
+
+template <size_t... I>
+constexpr std::array<StepKernel, sizeof...(I)> step_kernel_table(std::index_sequence<I...>) {
+  return {{step_kernel_or_null<I / 12, I / 4 % 3, (I / 2 % 2) != 0, (I % 2) != 0>()...}};
+}
+template <size_t... I>
+constexpr std::array<ThresholdKernel, sizeof...(I)> threshold_kernel_table(std::index_sequence<I...>) {
+  return {{sched_threshold_kernel<I / 2, (I % 2) != 0>...}};
+}
+static constexpr auto kStepKernels = step_kernel_table(std::make_index_sequence<3 * 3 * 2 * 2>{});
+static constexpr auto kThresholdKernels = threshold_kernel_table(std::make_index_sequence<3 * 2>{});
+static_assert(step_slot(SCHED_MULTISTEP, PRED_V, true, true) == 35 && threshold_slot(PRED_V, true) == 5, "slot functions and tables agree");
+
+// reads p's x, eps, eps_uncond, guidance, table, step_dev, step, the ranks and the shape; writes the B thresholds to p.scale
+int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred) {
+  const long per_sample = (long)p.C * p.H * p.W;
+  const bool guided = p.eps_uncond != nullptr;
+  ADM_REQUIRE(p.B > 0 && p.W % 4 == 0, "sched_threshold: W must be a multiple of 4");
   ADM_REQUIRE(per_sample > 0 && per_sample < (1L << 31), "sched_threshold: C*H*W must be below 2^31");
-  ADM_REQUIRE(lo >= 0 && hi >= lo && hi - lo <= 1 && hi < per_sample, "sched_threshold: need 0 <= lo <= hi <= C*H*W - 1 and hi - lo <= 1");
-  ADM_REQUIRE(w >= 0.f && w < 1.f, "sched_threshold: the interpolation weight must be in [0, 1)");
-  ADM_REQUIRE(max_value >= 1.f, "sched_threshold: max_value must be >= 1");
+  ADM_REQUIRE(p.lo >= 0 && p.hi >= p.lo && p.hi - p.lo <= 1 && p.hi < per_sample,
+              "sched_threshold: need 0 <= lo <= hi <= C*H*W - 1 and hi - lo <= 1");
+  ADM_REQUIRE(p.w >= 0.f && p.w < 1.f, "sched_threshold: the interpolation weight must be in [0, 1)");
+  ADM_REQUIRE(p.max_value >= 1.f, "sched_threshold: max_value must be >= 1");
   ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_threshold: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
-  const dim3 grid(B), block(kThreshThreads);
-  if (eps_uncond != nullptr) {
-    ADM_REQUIRE(std::isfinite(guidance), "sched_threshold: the guidance scale must be finite");
-    if (pred == PRED_SAMPLE)
-      ADM_LAUNCH(sched_threshold_guided_kernel<PRED_SAMPLE>, grid, block, 0, st, x, eps, eps_uncond, guidance, table, step_dev, step,
-                 per_sample, (unsigned)lo, (unsigned)hi, w, max_value, scale);
-    else if (pred == PRED_V)
-      ADM_LAUNCH(sched_threshold_guided_kernel<PRED_V>, grid, block, 0, st, x, eps, eps_uncond, guidance, table, step_dev, step,
-                 per_sample, (unsigned)lo, (unsigned)hi, w, max_value, scale);
-    else
-      ADM_LAUNCH(sched_threshold_guided_kernel<PRED_EPSILON>, grid, block, 0, st, x, eps, eps_uncond, guidance, table, step_dev, step,
-                 per_sample, (unsigned)lo, (unsigned)hi, w, max_value, scale);
-    return ADM_CHECK_LAUNCH();
-  }
-  if (pred == PRED_SAMPLE)
-    ADM_LAUNCH(sched_threshold_pred_kernel<PRED_SAMPLE>, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo,
-               (unsigned)hi, w, max_value, scale);
-  else if (pred == PRED_V)
-    ADM_LAUNCH(sched_threshold_pred_kernel<PRED_V>, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo,
-               (unsigned)hi, w, max_value, scale);
-  else
-    ADM_LAUNCH(sched_threshold_kernel, grid, block, 0, st, x, eps, table, step_dev, step, per_sample, (unsigned)lo, (unsigned)hi, w,
-               max_value, scale);
+  if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_threshold: the guidance scale must be finite");
+  const ThresholdKernel kernel = kThresholdKernels[threshold_slot(pred, guided)];
+  ADM_LAUNCH(kernel, dim3(p.B), dim3(kThreshThreads), 0, st, p.x, p.eps, p.eps_uncond, p.guidance, p.table, p.step_dev, p.step, per_sample,
+             (unsigned)p.lo, (unsigned)p.hi, p.w, p.max_value, p.scale);
   return ADM_CHECK_LAUNCH();
 }
 
@@ -507,74 +487,30 @@ int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offs
   return ADM_CHECK_LAUNCH();
 }
 
-template <int MODE>
-static int launch_philox_step(const SchedStepParams& p, dim3 grid, dim3 block, hipStream_t st, int pred, bool guided) {
-  if (guided) {
-    if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_SAMPLE, true>), grid, block, 0, st, p);
-    else if (pred == PRED_V) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_V, true>), grid, block, 0, st, p);
-    else ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_EPSILON, true>), grid, block, 0, st, p);
-  }
-  else if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_SAMPLE, false>), grid, block, 0, st, p);
-  else if (pred == PRED_V) ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_V, false>), grid, block, 0, st, p);
-  else ADM_LAUNCH((sched_step_philox_kernel<MODE, PRED_EPSILON, false>), grid, block, 0, st, p);
-  return ADM_CHECK_LAUNCH();
-}
-
 // SCHED_THRESH: selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written
 int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int pred) {
+  ADM_REQUIRE(mode >= SCHED_PLAIN && mode <= SCHED_MULTISTEP, "sched_step: mode must be 0 (plain), 1 (thresholded) or 2 (multistep)");
   ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_step: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
-  ADM_REQUIRE(pred == PRED_EPSILON || mode != SCHED_MULTISTEP, "sched_multistep: prediction must be 0 (the multistep step is epsilon only)");
   SchedStepParams p = in;
   p.per_sample = (long)p.C * p.H * p.W;
   p.n4 = p.per_sample * p.B / 4;
   p.mask_bstride = (long)p.n_mask_steps * p.per_sample;
-  const dim3 grid(ew_grid(p.n4)), block(256);
-  const bool guided = p.eps_uncond != nullptr;
+  const bool guided = p.eps_uncond != nullptr, philox = p.philox != 0;
+  ADM_REQUIRE(p.W % 4 == 0, "sched_step: W must be a multiple of 4");
+  ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
   if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_step: the guidance scale must be finite");
-  if (p.philox) {   // noise drawn in the kernel: the key, row offset and stream id from *p.nblock, or from p.nvals when it is null
-    ADM_REQUIRE(mode == SCHED_PLAIN || mode == SCHED_THRESH, "sched_step_philox: the multistep step has no noise rows");
-    ADM_REQUIRE(p.noise == nullptr, "sched_step_philox: a noise buffer and the noise stream exclude each other");
-    ADM_REQUIRE(p.B > 0 && p.per_sample > 0 && p.per_sample % 4 == 0, "sched_step_philox: C*H*W must be a positive multiple of 4");
-    ADM_REQUIRE(p.W % 4 == 0, "sched_step_philox: W must be a multiple of 4");
-    ADM_REQUIRE(p.per_sample / 4 <= 0xffffffffL, "sched_step_philox: C*H*W / 4 must fit in 32 bits (the counter's first word)");
-    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_philox: mask path requires C == 1 (as in the reference)");
-    if (mode == SCHED_THRESH) {
-      ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,
-                                     p.W, st, pred, p.eps_uncond, p.guidance));
-      return launch_philox_step<SCHED_THRESH>(p, grid, block, st, pred, guided);
-    }
-    return launch_philox_step<SCHED_PLAIN>(p, grid, block, st, pred, guided);
+  if (philox) {   // noise drawn in the kernel: the key, row offset and stream id from *p.nblock, or from p.nvals when it is null
+    ADM_REQUIRE(p.noise == nullptr, "sched_step: a noise buffer and the noise stream exclude each other");
+    ADM_REQUIRE(p.B > 0 && p.per_sample > 0 && p.per_sample % 4 == 0, "sched_step: C*H*W must be a positive multiple of 4");
+    ADM_REQUIRE(p.per_sample / 4 <= 0xffffffffL, "sched_step: C*H*W / 4 must fit in 32 bits (the counter's first word)");
   }
-  if (mode == SCHED_THRESH) {
-    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step_thresholded: mask path requires C == 1 (as in the reference)");
-    ADM_TRY(launch_sched_threshold(p.x, p.eps, p.table, p.step_dev, p.step, p.lo, p.hi, p.w, p.max_value, p.scale, p.B, p.C, p.H,
-                                   p.W, st, pred, p.eps_uncond, p.guidance));
-    if (guided) {
-      if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_guided_kernel<SCHED_THRESH, PRED_SAMPLE>), grid, block, 0, st, p);
-      else if (pred == PRED_V) ADM_LAUNCH((sched_step_guided_kernel<SCHED_THRESH, PRED_V>), grid, block, 0, st, p);
-      else ADM_LAUNCH((sched_step_guided_kernel<SCHED_THRESH, PRED_EPSILON>), grid, block, 0, st, p);
-    }
-    else if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_SAMPLE>), grid, block, 0, st, p);
-    else if (pred == PRED_V) ADM_LAUNCH((sched_step_pred_kernel<SCHED_THRESH, PRED_V>), grid, block, 0, st, p);
-    else ADM_LAUNCH(sched_step_kernel<SCHED_THRESH>, grid, block, 0, st, p);
-  } else if (mode == SCHED_MULTISTEP) {
-    ADM_REQUIRE(p.W % 4 == 0, "sched_multistep: W must be a multiple of 4");
-    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_multistep: mask path requires C == 1 (as in the reference)");
-    if (guided) ADM_LAUNCH((sched_step_guided_kernel<SCHED_MULTISTEP, PRED_EPSILON>), grid, block, 0, st, p);
-    else ADM_LAUNCH(sched_step_kernel<SCHED_MULTISTEP>, grid, block, 0, st, p);
-  } else {
-    ADM_REQUIRE(mode == SCHED_PLAIN, "sched_step: unknown mode");
-    ADM_REQUIRE(p.W % 4 == 0, "sched_step: W must be a multiple of 4");
-    ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
-    if (guided) {
-      if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_guided_kernel<SCHED_PLAIN, PRED_SAMPLE>), grid, block, 0, st, p);
-      else if (pred == PRED_V) ADM_LAUNCH((sched_step_guided_kernel<SCHED_PLAIN, PRED_V>), grid, block, 0, st, p);
-      else ADM_LAUNCH((sched_step_guided_kernel<SCHED_PLAIN, PRED_EPSILON>), grid, block, 0, st, p);
-    }
-    else if (pred == PRED_SAMPLE) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_SAMPLE>), grid, block, 0, st, p);
-    else if (pred == PRED_V) ADM_LAUNCH((sched_step_pred_kernel<SCHED_PLAIN, PRED_V>), grid, block, 0, st, p);
-    else ADM_LAUNCH(sched_step_kernel<SCHED_PLAIN>, grid, block, 0, st, p);
+  const StepKernel kernel = kStepKernels[step_slot(mode, pred, guided, philox)];
+  if (kernel == nullptr) {   // the two reasons a multistep combination is not built
+    ADM_REQUIRE(pred == PRED_EPSILON, "sched_step: prediction must be 0 (the multistep step is epsilon only)");
+    ADM_FAIL("sched_step: the multistep step has no noise rows");
   }
+  if (mode == SCHED_THRESH) ADM_TRY(launch_sched_threshold(p, st, pred));
+  ADM_LAUNCH(kernel, dim3(ew_grid(p.n4)), dim3(256), 0, st, p);
   return ADM_CHECK_LAUNCH();
 }
 

@@ -343,19 +343,13 @@ static int ensure_khist(adm_unet* h, const float* k_hist_host, int n, hipStream_
   return copy_h2d(h->khist_dev, k_hist_host, sizeof(float) * (size_t)n, st);
 }
 
-enum { LOOP_ENCODE = -1 };   // LoopArgs::mode: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
-
-struct LoopArgs {
-  float* x; int B; int n_steps; const float* step_noise; const float* mask; int mask_start, mask_end;
-  uint8_t* u8; int mode; const float* k_hist_host;
-  int th_lo = 0, th_hi = 0; float th_w = 0.f, th_max = 1.f;   // SCHED_THRESH: the two ranks, their weight and sample_max_value
-  int pred = PRED_EPSILON;                                    // what the model output is: chooses the step (and selection) kernel
-  // classifier-free guidance (both set, or neither): the unconditional encoding, device, of the shape of the handle's encoding, and the scale
-  const float* ctx_uncond = nullptr; float guidance = 1.f;
-  // noise drawn inside the step kernel ("adm noise stream 1"): the seed and the global row of x[0]. They reach the kernel through the
-  // handle's device block, never as kernel arguments: neither is part of the captured graph's key.
-  bool philox = false; uint64_t seed = 0; int row_offset = 0;
-};
+// adm_sample_loop_args::mode inside this file: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
+// (adm_encode_loop only; adm_sample_loop_ex refuses it)
+enum { LOOP_ENCODE = -1 };
+using LoopArgs = adm_sample_loop_args;
+// LoopArgs::encoding_uncond and guidance_scale: classifier-free guidance (the unconditional encoding, device, of the shape of the handle's).
+// LoopArgs::seed and row_offset (noise_source 1, "adm noise stream 1": the seed and the global row of x[0]) reach the kernel through the
+// handle's device block, never as kernel arguments: neither is part of the captured graph's key.
 
 // The noise-stream block, written in stream order before the first step and outside the captured step.
 static int ensure_noise_block(adm_unet* h, const LoopArgs& a, hipStream_t st) {
@@ -370,12 +364,12 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
   const adm_unet_config& c = h->cfg;
   const adm_sched_coef* table = h->coef_dev;
   ADM_TRY(run_forward(h, a.x, h->eps_buf, a.B, table, st));
-  if (a.ctx_uncond != nullptr) {
+  if (a.encoding_uncond != nullptr) {
     // The unconditional branch: a second forward of batch B on the SAME plan (its side-stream hoists included), with the encoding pointer
     // swapped. Nothing derived from the encoding outlives a forward (the cross-attention kernel projects K and V from net.ctx inside every
     // launch), so the swap is all it takes; both forwards run in stream order, the second after the first has joined its side launches.
     const float* ctx_cond = h->net.ctx;
-    h->net.ctx = a.ctx_uncond;
+    h->net.ctx = a.encoding_uncond;
     const int rc = run_forward(h, a.x, h->eps_uncond_buf, a.B, table, st);
     h->net.ctx = ctx_cond;
     ADM_TRY(rc);
@@ -384,31 +378,33 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
   if (a.mode == LOOP_ENCODE) {
     ADM_TRY(launch_encode_step(a.x, h->eps_buf, table, h->step_dev, step, n, st));
   } else {
-    SchedStepParams p{a.x, h->eps_buf, a.step_noise, a.x, a.u8, table, h->step_dev, step, a.mask, a.n_steps, a.mask_start,
+    SchedStepParams p{a.x, h->eps_buf, a.step_noise, a.x, a.u8_out, table, h->step_dev, step, a.mask, a.n_steps, a.mask_start,
                       a.mask_end, a.B, c.in_channels, c.sample_h, c.sample_w};
     p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
-    p.lo = a.th_lo; p.hi = a.th_hi; p.w = a.th_w; p.max_value = a.th_max; p.scale = h->scale_buf;
+    p.lo = a.lo; p.hi = a.hi; p.w = a.w; p.max_value = a.max_value; p.scale = h->scale_buf;
     p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
-    if (a.ctx_uncond != nullptr) { p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance; }
-    if (a.philox) { p.philox = 1; p.nblock = h->noise_blk_dev; }
-    ADM_TRY(launch_sched_step(p, a.mode, st, a.pred));
+    if (a.encoding_uncond != nullptr) { p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance_scale; }
+    if (a.noise_source == 1) { p.philox = 1; p.nblock = h->noise_blk_dev; }
+    ADM_TRY(launch_sched_step(p, a.mode, st, a.prediction));
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
   return 0;
 }
 
-static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_host, int use_graph, hipStream_t st) {
+static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
+  const adm_sched_coef* coef_host = a.coef_host;
+  const int use_graph = a.use_graph;
   ADM_TRY(finalize(h));
   ADM_REQUIRE(h->cfg.in_channels == h->cfg.out_channels, "sample_loop: in/out channels differ");
   ADM_TRY(plan(h, a.B));
-  if (a.ctx_uncond != nullptr && h->eps_uncond_buf == nullptr)
+  if (a.encoding_uncond != nullptr && h->eps_uncond_buf == nullptr)
     ADM_TRY(extra_alloc(h, (void**)&h->eps_uncond_buf,
                         sizeof(float) * (size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
 #if defined(ADM_EMU)
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
-  if (a.philox) ADM_TRY(ensure_noise_block(h, a, st));
+  if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, st));
   for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
   return 0;
 #else
@@ -423,28 +419,28 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
   }
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, run));
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
-  if (a.philox) ADM_TRY(ensure_noise_block(h, a, run));
+  if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, run));
   if (!use_graph) {
     for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
   } else {
     std::vector<uint64_t> key = {(uint64_t)a.x, (uint64_t)a.B, (uint64_t)a.n_steps, (uint64_t)a.step_noise,
-                                 (uint64_t)a.mask, (uint64_t)a.mask_start, (uint64_t)a.mask_end, (uint64_t)a.u8,
+                                 (uint64_t)a.mask, (uint64_t)a.mask_start, (uint64_t)a.mask_end, (uint64_t)a.u8_out,
                                  (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
-                                 (uint64_t)h->net.ctx_S, (uint64_t)a.pred};   // (pred: the kernel itself is baked into the captured node)
+                                 (uint64_t)h->net.ctx_S, (uint64_t)a.prediction};   // (pred: the kernel itself is baked into the captured node)
     if (a.mode == SCHED_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
     if (a.mode == SCHED_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
       uint32_t wb, mb;
-      memcpy(&wb, &a.th_w, 4); memcpy(&mb, &a.th_max, 4);
-      key.push_back((uint64_t)h->scale_buf); key.push_back((uint64_t)a.th_lo); key.push_back((uint64_t)a.th_hi);
+      memcpy(&wb, &a.w, 4); memcpy(&mb, &a.max_value, 4);
+      key.push_back((uint64_t)h->scale_buf); key.push_back((uint64_t)a.lo); key.push_back((uint64_t)a.hi);
       key.push_back(wb); key.push_back(mb);
     }
-    if (a.ctx_uncond != nullptr) {  // the second forward's encoding and output, and the scale: all baked into the captured nodes
+    if (a.encoding_uncond != nullptr) {  // the second forward's encoding and output, and the scale: all baked into the captured nodes
       uint32_t gb;
-      memcpy(&gb, &a.guidance, 4);
-      key.push_back((uint64_t)a.ctx_uncond); key.push_back((uint64_t)h->eps_uncond_buf); key.push_back(0x100000000ull | gb);
+      memcpy(&gb, &a.guidance_scale, 4);
+      key.push_back((uint64_t)a.encoding_uncond); key.push_back((uint64_t)h->eps_uncond_buf); key.push_back(0x100000000ull | gb);
     }
     // the noise stream: the block's address (the handle's, stable) and nothing else; the seed and the row offset are data behind it
-    if (a.philox) { key.push_back(0x200000000ull); key.push_back((uint64_t)h->noise_blk_dev); }
+    if (a.noise_source == 1) { key.push_back(0x200000000ull); key.push_back((uint64_t)h->noise_blk_dev); }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
         // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
@@ -486,12 +482,12 @@ static int run_loop(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_h
 }
 
 // What every loop entry point does after its own argument checks.
-static int run_loop_fp32(adm_unet* h, const LoopArgs& a, const adm_sched_coef* coef_host, int use_graph, void* stream) {
+static int run_loop_fp32(adm_unet* h, const LoopArgs& a, void* stream) {
   Bf16Scope fp32(0);
   ADM_TRY(finalize(h));
   InferenceScope inf(&h->net, (hipStream_t)stream);
   ADM_TRY(inf.rc);
-  return run_loop(h, a, coef_host, use_graph, (hipStream_t)stream);
+  return run_loop(h, a, (hipStream_t)stream);
 }
 
 }  // namespace adm
@@ -718,98 +714,112 @@ int adm_unet_plan_ops(adm_unet_t* h, int B, adm_plan_op* recs, int cap, int* n_o
   return h->net.plan_report(h->temb_all, h->temb_rows, recs, cap, n_out);
 }
 
+// The sampling loop: all argument checks are here.
+int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream) {
+  ADM_REQUIRE(h && a && a->x && a->coef_host && a->n_steps > 0, "sample_loop: bad argument");
+  ADM_REQUIRE(a->mode >= SCHED_PLAIN && a->mode <= SCHED_MULTISTEP, "sample_loop: mode must be 0 (plain), 1 (thresholded) or 2 (multistep)");
+  ADM_REQUIRE(a->noise_source == 0 || a->noise_source == 1, "sample_loop: noise_source must be 0 (step_noise, or none) or 1 (adm noise stream 1)");
+  if (a->encoding_uncond != nullptr) {   // guided; NULL: unguided, and the model may be unconditional
+    ADM_REQUIRE(h->cfg.cross_attention_dim > 0, "sample_loop: this model has no cross-attention (UNet2DModel): nothing to guide");
+    ADM_REQUIRE(h->net.ctx != nullptr && h->net.ctx_S > 0, "sample_loop: no encoding set (adm_unet_set_encoding)");
+    ADM_REQUIRE(std::isfinite(a->guidance_scale), "sample_loop: the guidance scale must be finite");
+  }
+  ADM_REQUIRE(a->prediction >= PRED_EPSILON && a->prediction <= PRED_V, "sample_loop: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  if (a->mode == SCHED_MULTISTEP) {
+    ADM_REQUIRE(a->k_hist_host != nullptr, "sample_loop: the multistep loop needs k_hist_host");
+    ADM_REQUIRE(a->prediction == PRED_EPSILON, "sample_loop: the multistep loop is epsilon only and not thresholded");
+    ADM_REQUIRE(a->noise_source == 0, "sample_loop: the multistep step has no noise rows");
+    ADM_REQUIRE(a->k_hist_host[0] == 0.f, "sample_loop: the first row of a run must be first order (k_hist[0] == 0)");
+  }
+  if (a->noise_source == 1) {
+    ADM_REQUIRE(a->B > 0, "sample_loop: bad argument");
+    ADM_REQUIRE(a->step_noise == nullptr, "sample_loop: a noise buffer and the noise stream exclude each other");
+    ADM_REQUIRE(a->row_offset >= 0, "sample_loop: row_offset must be >= 0");
+    ADM_REQUIRE((uint64_t)a->row_offset + (uint64_t)a->B <= 0xffffffffull, "sample_loop: row_offset + B must fit in 32 bits");
+    ADM_REQUIRE(((long)h->cfg.in_channels * h->cfg.sample_h * h->cfg.sample_w) % 4 == 0, "sample_loop: C*H*W must be a multiple of 4");
+    for (int i = 0; i < a->n_steps; ++i)   // the counter's third word is the row's timestep as an integer
+      ADM_REQUIRE(a->coef_host[i].timestep >= 0.f && a->coef_host[i].timestep < 2147483648.f, "sample_loop: every timestep must be in [0, 2^31)");
+  }
+  return run_loop_fp32(h, *a, stream);
+}
+
+// ---- the frozen positional entry points (include/adm.h): a struct fill and one call each
+static adm_sample_loop_args loop_args(float* x, int B, const adm_sched_coef* coef_host, int n_steps, const float* step_noise, const float* mask,
+                                      int mask_start, int mask_end, uint8_t* u8_out, int use_graph) {
+  adm_sample_loop_args a{};
+  a.x = x; a.B = B; a.coef_host = coef_host; a.n_steps = n_steps; a.step_noise = step_noise; a.mask = mask; a.mask_start = mask_start;
+  a.mask_end = mask_end; a.u8_out = u8_out; a.use_graph = use_graph;
+  return a;
+}
+// thresholded == 0: the static clamp, and lo, hi, w, max_value are ignored
+static void loop_args_threshold(adm_sample_loop_args& a, int thresholded, int lo, int hi, float w, float max_value) {
+  if (!thresholded) return;
+  a.mode = SCHED_THRESH; a.lo = lo; a.hi = hi; a.w = w; a.max_value = max_value;
+}
+
 int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                     const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out,
                     int use_graph, void* stream) {
-  ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop: bad argument");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_PLAIN, nullptr};
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  const adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, step_noise, mask, mask_start, mask_end, u8_out, use_graph);
+  return adm_sample_loop_ex(h, &a, stream);
 }
 
 int adm_sample_loop_multistep(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host,
                               int n_steps, const float* step_noise, const float* mask, int mask_start, int mask_end,
                               uint8_t* u8_out, int use_graph, void* stream) {
-  ADM_REQUIRE(h && x && coef_host && k_hist_host && n_steps > 0, "sample_loop_multistep: bad argument");
-  ADM_REQUIRE(k_hist_host[0] == 0.f, "sample_loop_multistep: the first row of a run must be first order (k_hist[0] == 0)");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_MULTISTEP, k_hist_host};
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, step_noise, mask, mask_start, mask_end, u8_out, use_graph);
+  a.mode = SCHED_MULTISTEP; a.k_hist_host = k_hist_host;
+  return adm_sample_loop_ex(h, &a, stream);
 }
 
 int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                                 const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out,
                                 int use_graph, void* stream, int lo, int hi, float w, float max_value) {
-  ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop_thresholded: bad argument");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, SCHED_THRESH, nullptr};
-  a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value;
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, step_noise, mask, mask_start, mask_end, u8_out, use_graph);
+  loop_args_threshold(a, 1, lo, hi, w, max_value);
+  return adm_sample_loop_ex(h, &a, stream);
 }
 
 int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, const float* step_noise,
                          const float* mask, int mask_start, int mask_end, uint8_t* u8_out, int use_graph, void* stream, int lo,
                          int hi, float w, float max_value, int thresholded, int prediction) {
-  ADM_REQUIRE(h && x && coef_host && n_steps > 0, "sample_loop_pred: bad argument");
-  ADM_REQUIRE(prediction >= PRED_EPSILON && prediction <= PRED_V,
-              "sample_loop_pred: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, thresholded ? SCHED_THRESH : SCHED_PLAIN, nullptr};
-  if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
-  a.pred = prediction;
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, step_noise, mask, mask_start, mask_end, u8_out, use_graph);
+  loop_args_threshold(a, thresholded, lo, hi, w, max_value);
+  a.prediction = prediction;
+  return adm_sample_loop_ex(h, &a, stream);
 }
 
 int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host, int n_steps,
                            const float* step_noise, const float* mask, int mask_start, int mask_end, uint8_t* u8_out, int use_graph,
                            void* stream, int lo, int hi, float w, float max_value, int thresholded, int prediction,
                            const float* encoding_uncond_dev, float guidance_scale) {
-  ADM_REQUIRE(h && x && coef_host && n_steps > 0 && encoding_uncond_dev, "sample_loop_guided: bad argument");
-  ADM_REQUIRE(h->cfg.cross_attention_dim > 0, "sample_loop_guided: this model has no cross-attention (UNet2DModel): nothing to guide");
-  ADM_REQUIRE(h->net.ctx != nullptr && h->net.ctx_S > 0, "sample_loop_guided: no encoding set (adm_unet_set_encoding)");
-  ADM_REQUIRE(std::isfinite(guidance_scale), "sample_loop_guided: the guidance scale must be finite");
-  ADM_REQUIRE(prediction >= PRED_EPSILON && prediction <= PRED_V,
-              "sample_loop_guided: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
-  int mode = thresholded ? SCHED_THRESH : SCHED_PLAIN;
-  if (k_hist_host != nullptr) {
-    ADM_REQUIRE(!thresholded && prediction == PRED_EPSILON, "sample_loop_guided: the multistep loop is epsilon only and not thresholded");
-    ADM_REQUIRE(k_hist_host[0] == 0.f, "sample_loop_guided: the first row of a run must be first order (k_hist[0] == 0)");
-    mode = SCHED_MULTISTEP;
-  }
-  LoopArgs a{x, B, n_steps, step_noise, mask, mask_start, mask_end, u8_out, mode, k_hist_host};
-  if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
-  a.pred = prediction;
-  a.ctx_uncond = encoding_uncond_dev; a.guidance = guidance_scale;
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  ADM_REQUIRE(encoding_uncond_dev != nullptr, "sample_loop_guided: bad argument");   // (NULL means "unguided" to the struct)
+  // (`thresholded` together with k_hist_host: the struct has one mode and cannot say it)
+  ADM_REQUIRE(k_hist_host == nullptr || !thresholded, "sample_loop_guided: the multistep loop is epsilon only and not thresholded");
+  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, step_noise, mask, mask_start, mask_end, u8_out, use_graph);
+  loop_args_threshold(a, thresholded, lo, hi, w, max_value);
+  if (k_hist_host != nullptr) { a.mode = SCHED_MULTISTEP; a.k_hist_host = k_hist_host; }
+  a.prediction = prediction; a.encoding_uncond = encoding_uncond_dev; a.guidance_scale = guidance_scale;
+  return adm_sample_loop_ex(h, &a, stream);
 }
 
 int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, const float* mask, int mask_start,
                            int mask_end, uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
                            int thresholded, int prediction, const float* encoding_uncond_dev, float guidance_scale, uint64_t seed,
                            int row_offset) {
-  ADM_REQUIRE(h && x && coef_host && n_steps > 0 && B > 0, "sample_loop_philox: bad argument");
-  ADM_REQUIRE(prediction >= PRED_EPSILON && prediction <= PRED_V,
-              "sample_loop_philox: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
-  ADM_REQUIRE(row_offset >= 0, "sample_loop_philox: row_offset must be >= 0");
-  ADM_REQUIRE((uint64_t)row_offset + (uint64_t)B <= 0xffffffffull, "sample_loop_philox: row_offset + B must fit in 32 bits");
-  ADM_REQUIRE(((long)h->cfg.in_channels * h->cfg.sample_h * h->cfg.sample_w) % 4 == 0,
-              "sample_loop_philox: C*H*W must be a multiple of 4");
-  for (int i = 0; i < n_steps; ++i)   // the counter's third word is the row's timestep as an integer
-    ADM_REQUIRE(coef_host[i].timestep >= 0.f && coef_host[i].timestep < 2147483648.f, "sample_loop_philox: every timestep must be in [0, 2^31)");
-  LoopArgs a{x, B, n_steps, nullptr, mask, mask_start, mask_end, u8_out, thresholded ? SCHED_THRESH : SCHED_PLAIN, nullptr};
-  if (thresholded) { a.th_lo = lo; a.th_hi = hi; a.th_w = w; a.th_max = max_value; }
-  a.pred = prediction;
-  if (encoding_uncond_dev != nullptr) {   // guided, as adm_sample_loop_guided; NULL: unguided, and the model may be unconditional
-    ADM_REQUIRE(h->cfg.cross_attention_dim > 0, "sample_loop_philox: this model has no cross-attention (UNet2DModel): nothing to guide");
-    ADM_REQUIRE(h->net.ctx != nullptr && h->net.ctx_S > 0, "sample_loop_philox: no encoding set (adm_unet_set_encoding)");
-    ADM_REQUIRE(std::isfinite(guidance_scale), "sample_loop_philox: the guidance scale must be finite");
-    a.ctx_uncond = encoding_uncond_dev; a.guidance = guidance_scale;
-  }
-  a.philox = true; a.seed = seed; a.row_offset = row_offset;
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, nullptr, mask, mask_start, mask_end, u8_out, use_graph);
+  loop_args_threshold(a, thresholded, lo, hi, w, max_value);
+  a.prediction = prediction; a.encoding_uncond = encoding_uncond_dev; a.guidance_scale = guidance_scale;
+  a.noise_source = 1; a.seed = seed; a.row_offset = row_offset;
+  return adm_sample_loop_ex(h, &a, stream);
 }
 
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream) {
   ADM_REQUIRE(h && x && coef_host && n_steps > 0, "encode_loop: bad argument");
-  LoopArgs a{x, B, n_steps, nullptr, nullptr, 0, 0, nullptr, LOOP_ENCODE, nullptr};
-  return run_loop_fp32(h, a, coef_host, use_graph, stream);
+  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, nullptr, nullptr, 0, 0, nullptr, use_graph);
+  a.mode = LOOP_ENCODE;
+  return run_loop_fp32(h, a, stream);
 }
 
 }  // extern "C"

@@ -236,6 +236,45 @@ int adm_sched_step_philox(const float* x, const float* eps_cond, const float* ep
                           int lo, int hi, float w, float max_value, float* scale, int prediction,
                           uint64_t seed, int row_offset);
 
+/* The scheduler step as ONE entry point (adm_version() >= 114). Every combination above, and each one a later version adds, is a
+ * value of this struct: new scheduler features add fields at its end and bump adm_version(), as adm_conv_args does, and add no symbol.
+ * Zero-initialise it and set what the call uses.
+ *
+ * FROZEN: adm_sched_step, adm_sched_multistep, adm_sched_threshold, adm_sched_step_thresholded, adm_sched_threshold_pred,
+ * adm_sched_step_pred, adm_sched_threshold_guided, adm_sched_step_guided and adm_sched_step_philox keep their signatures and their
+ * results for existing callers; each fills this struct and calls adm_sched_step_ex / adm_sched_threshold_ex. None of them will grow. */
+typedef struct adm_sched_step_args {
+  const float* x;            /* (B,C,H,W) */
+  const float* eps;          /* the model output (the conditional one under guidance) */
+  const float* eps_uncond;   /* NULL: unguided, guidance_scale is ignored; otherwise the unconditional output and a finite scale */
+  float guidance_scale;
+  const float* noise;        /* NULL or (B,C,H,W); must be NULL with noise_source 1 */
+  float* out;                /* may alias x */
+  uint8_t* u8_out;           /* NULL or (B,H*W*C) */
+  const adm_sched_coef* coef_table;
+  const float* k_hist_table; /* mode 2: one float per row of coef_table */
+  float* hist;               /* mode 2: (B,C,H,W), see adm_sched_multistep */
+  const int* step_dev;       /* row used = step_dev ? *step_dev : step */
+  int step;
+  const float* mask;         /* NULL or (B,n_mask_steps,H,W); needs C == 1 */
+  int n_mask_steps, mask_start, mask_end;
+  int B, C, H, W;            /* W % 4 == 0 */
+  int mode;                  /* 0 plain (the row's static clip), 1 thresholded (needs scale), 2 multistep (needs k_hist_table and hist;
+                                prediction 0, noise_source 0 and scale == NULL: that step is epsilon only, has no noise rows and no
+                                thresholded form) */
+  int prediction;            /* 0 epsilon, 1 sample, 2 v_prediction */
+  int lo, hi;                /* mode 1, and adm_sched_threshold_ex: the ranks, weight and maximum of adm_sched_threshold */
+  float w, max_value;
+  float* scale;              /* mode 1, and adm_sched_threshold_ex: (B,) device, receives s_b */
+  int noise_source;          /* 0: `noise` (or none); 1: "adm noise stream 1", stream 0, drawn in the kernel from (seed, row_offset + b) */
+  uint64_t seed;
+  int row_offset;            /* noise_source 1: >= 0 and row_offset + B within 32 bits */
+} adm_sched_step_args;
+int adm_sched_step_ex(const adm_sched_step_args* a, void* stream);
+/* The selection alone (adm_sched_threshold and its _pred / _guided forms): reads x, eps, eps_uncond, guidance_scale, coef_table, step_dev,
+ * step, B, C, H, W, prediction, lo, hi, w, max_value of the same struct and writes scale; the other fields are ignored. */
+int adm_sched_threshold_ex(const adm_sched_step_args* a, void* stream);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -533,6 +572,33 @@ int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef*
                            uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
                            int thresholded, int prediction, const float* encoding_uncond_dev, float guidance_scale,
                            uint64_t seed, int row_offset);
+/* The sampling loop as ONE entry point (adm_version() >= 114); the struct grows as adm_sched_step_args does, and no loop symbol is added.
+ * FROZEN: adm_sample_loop, adm_sample_loop_multistep, adm_sample_loop_thresholded, adm_sample_loop_pred, adm_sample_loop_guided and
+ * adm_sample_loop_philox keep their signatures and results; each fills this struct and calls adm_sample_loop_ex.
+ * mode, prediction, lo, hi, w, max_value, guidance_scale, noise_source, seed, row_offset: as adm_sched_step_args (the scale, history and
+ * second output buffers are the handle's). k_hist_host: mode 2, n_steps host floats, k_hist_host[0] == 0. encoding_uncond: NULL, or the
+ * device encoding of the unconditional branch (adm_sample_loop_guided). step_noise: NULL with noise_source 1. */
+typedef struct adm_sample_loop_args {
+  float* x;
+  int B;
+  const adm_sched_coef* coef_host;
+  const float* k_hist_host;
+  int n_steps;
+  const float* step_noise;
+  const float* mask;
+  int mask_start, mask_end;
+  uint8_t* u8_out;
+  int use_graph;
+  int mode, prediction;
+  int lo, hi;
+  float w, max_value;
+  const float* encoding_uncond;
+  float guidance_scale;
+  int noise_source;
+  uint64_t seed;
+  int row_offset;
+} adm_sample_loop_args;
+int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,

@@ -18,9 +18,7 @@ G. Refusals. I. Register check of every kernel of k_sched.hip. (H, two gloo rank
 import functools
 import math
 import os
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -30,7 +28,8 @@ import test_dpmsolver as td
 import test_guidance as tg
 import test_prediction_types as tp
 import test_thresholding as tt
-from native_backend import BACKENDS, select
+import sched_kernels
+from native_backend import BACKENDS, select, spy_sample_loop
 from oracle import mel as omel
 from oracle import pipeline as opipe
 from oracle import schedulers as osched
@@ -328,23 +327,17 @@ def test_loop_invariances_bit_for_bit(backend):
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_the_loop_is_one_native_call_without_a_noise_tensor(backend, monkeypatch):
     """More steps than one staging chunk holds: the host-noise path needs two calls, the device-noise path one."""
-    from audiodiffusion import _native as N
     dev = select(backend)
     pipe = _tiny_pipe()
     monkeypatch.setattr(type(pipe), "_STEP_CHUNK", 2)
-    real, calls = N.lib(), []
-
-    class Spy:
-        def __getattr__(self, name):
-            if name.startswith("adm_sample_loop"):
-                calls.append(name)
-            return getattr(real, name)
-    monkeypatch.setattr(N, "lib", lambda: Spy())
+    calls = spy_sample_loop(monkeypatch)
     pipe(batch_size=1, steps=4, audio=False, device_noise_seed=SEED)
-    assert calls == ["adm_sample_loop_philox"]
+    assert [c["symbol"] for c in calls] == ["adm_sample_loop_ex"]
+    assert calls[0]["noise_source"] == 1 and calls[0]["step_noise"] is None and calls[0]["n_steps"] == 4 and calls[0]["seed"] == SEED
     del calls[:]
     pipe(batch_size=1, steps=4, audio=False, noise=_randn((1, 1, 16, 16), 1).to(dev), step_noise=_randn((4, 1, 1, 16, 16), 2).to(dev))
-    assert calls == ["adm_sample_loop"] * 2
+    assert [c["symbol"] for c in calls] == ["adm_sample_loop_ex"] * 2
+    assert all(c["noise_source"] == 0 and c["step_noise"] is not None and c["n_steps"] == 2 for c in calls)
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
@@ -552,21 +545,6 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_every_kernel_of_k_sched_compiles_without_scratch():
-    """The static check of tests/test_no_spill.py on k_sched.hip: the twelve noise-drawing step kernels and the fill kernel exist under
-    names of their own, and no kernel of the file uses scratch on gfx950."""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "audio-diffusion_amd", "csrc")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "k_sched.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=csrc, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            usage[name] = int(m.group(1))
-    assert len({k for k in usage if "sched_step_philox_kernel" in k}) == 12, usage     # {plain, thresholded} x 3 types x {guided, not}
-    assert any("randn_fill_kernel" in k for k in usage), usage
-    assert len(usage) >= 12 + 1 + 14, usage
-    assert all(v == 0 for v in usage.values()), {k: v for k, v in usage.items() if v}
+    """The static check of tests/test_no_spill.py on k_sched.hip: the twelve noise-drawing step kernels and the fill kernel exist, the
+    kernel set is exactly the dispatch tables', and no kernel of the file uses scratch on gfx950."""
+    sched_kernels.assert_kernel_set_and_no_scratch()

@@ -20,7 +20,7 @@ import torch
 import test_dpmsolver as td
 import test_prediction_types as tp
 import test_thresholding as tt
-from native_backend import BACKENDS, select
+from native_backend import BACKENDS, select, spy_sample_loop
 from oracle import mel as omel
 from oracle import pipeline as opipe
 from oracle import schedulers as osched
@@ -455,22 +455,16 @@ def test_guided_loop_bit_identities(backend, kind, cfg):
 
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_scale_at_most_one_never_reaches_the_guided_entry_point(backend, monkeypatch):
-    from audiodiffusion import _native as N
     dev = select(backend)
     _, mine = _build("ddim")
-    real, calls = N.lib(), []
-
-    class Spy:
-        def __getattr__(self, name):
-            calls.append(name)
-            return getattr(real, name)
-    monkeypatch.setattr(N, "lib", lambda: Spy())
+    calls = spy_sample_loop(monkeypatch)
     noise, enc = _randn((1, 1, 16, 16), 1).to(dev), _randn((1, 1, 12), 2).to(dev)
     for g in (None, 0.0, 1.0):
         mine(batch_size=1, steps=2, noise=noise.clone(), encoding=enc, audio=False, guidance_scale=g)
-    assert "adm_sample_loop" in calls and "adm_sample_loop_guided" not in calls
+    assert len(calls) == 3 and all(c["symbol"] == "adm_sample_loop_ex" and c["encoding_uncond"] is None for c in calls)
     mine(batch_size=1, steps=2, noise=noise.clone(), encoding=enc, audio=False, guidance_scale=1.0001)
-    assert "adm_sample_loop_guided" in calls
+    assert len(calls) == 4 and calls[3]["symbol"] == "adm_sample_loop_ex" and calls[3]["encoding_uncond"] is not None
+    assert calls[3]["guidance_scale"] == np.float32(1.0001)
 
 
 # ================================================================ F. plumbing

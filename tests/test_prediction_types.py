@@ -25,14 +25,13 @@ F. Plumbing. G. The companions (emulator only: no kernel).
 import ctypes as C
 import json
 import os
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import sched_kernels
 from native_backend import BACKENDS, select
 from oracle import mel as omel
 from oracle import pipeline as opipe
@@ -766,24 +765,9 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_new_kernels_compile_without_spills():
-    """The static check of tests/test_no_spill.py: the four step and the two selection instantiations of the new types and the training
-    prologue exist under names of their own and use no scratch."""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "audio-diffusion_amd", "csrc")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "k_sched.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=csrc, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            usage[name] = int(m.group(1))
-    assert len({k for k in usage if "sched_step_pred_kernel" in k}) == 4, usage      # {plain, thresholded} x {sample, v_prediction}
-    assert len({k for k in usage if "sched_threshold_pred_kernel" in k}) == 2, usage
-    assert any("noise_and_velocity_kernel" in k for k in usage), usage
-    assert all(v == 0 for v in usage.values()), usage
+    """The static check of tests/test_no_spill.py: the step and selection instantiations of the sample / v_prediction types and the
+    training prologue exist, the kernel set is exactly the dispatch tables', and nothing uses scratch."""
+    sched_kernels.assert_kernel_set_and_no_scratch()
 
 
 # ================================================================ G. the companions (no kernel: emulator only)

@@ -1,6 +1,6 @@
 """scripts/train_unet.py --prediction_type v_prediction end to end on the emulator: one epoch on the synthetic 16 x 16 dataset trains
 against the velocity (`ops.noise_and_velocity`: `noisy` and the target from one kernel), the saved scheduler_config.json carries the type,
-and the reloaded pipeline samples through the loop of that type (`adm_sample_loop_pred`)."""
+and the reloaded pipeline samples through the loop with that type (`adm_sample_loop_args.prediction`)."""
 import importlib.util
 import json
 import os
@@ -8,7 +8,7 @@ import os
 import pytest
 import torch
 
-from native_backend import select
+from native_backend import select, spy_sample_loop
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = dict(sample_size=(16, 16), in_channels=1, out_channels=1, layers_per_block=1, block_out_channels=(32, 64),
@@ -27,7 +27,6 @@ def _script(name):
 def test_training_script_with_a_prediction_type(kind, scheduler, tmp_path, monkeypatch):
     select("emu")
     from audiodiffusion import AudioDiffusionPipeline, DDPMScheduler, Mel, UNet2DModel
-    from audiodiffusion import _native as N
     from audiodiffusion import ops
     start = UNet2DModel(**TINY).init_random(3)
     AudioDiffusionPipeline(None, start, Mel(**MEL), DDPMScheduler()).save_pretrained(str(tmp_path / "start"))
@@ -84,17 +83,8 @@ def test_training_script_with_a_prediction_type(kind, scheduler, tmp_path, monke
     assert changed >= 0.9 * len(w0), f"only {changed} of {len(w0)} tensors moved"
     assert all(torch.isfinite(v).all() for v in w1.values())
     # the reloaded pipeline samples through the loop of its type
-    calls = []
-    real = N.lib().adm_sample_loop_pred
-
-    class _Lib:
-        def __getattr__(self, name):
-            if name == "adm_sample_loop_pred":
-                return lambda *a: (calls.append(a[-1]), real(*a))[1]
-            return getattr(real_lib, name)
-    real_lib = N.lib()
-    monkeypatch.setattr(N, "lib", lambda: _Lib())
+    calls = spy_sample_loop(monkeypatch)
     noise = torch.randn(1, 1, 16, 16, generator=torch.Generator().manual_seed(0))
     images, floats = pipe(batch_size=1, steps=3, noise=noise, step_noise=torch.randn(3, 1, 1, 16, 16), audio=False, return_float=True)
-    assert calls and set(calls) == {pipe.scheduler.prediction}
+    assert calls and all(c["symbol"] == "adm_sample_loop_ex" and c["prediction"] == pipe.scheduler.prediction for c in calls)
     assert images[0].size == (16, 16) and bool(torch.isfinite(floats).all())
