@@ -71,14 +71,14 @@ class AudioDiffusion:
     def generate_spectrogram_and_audio(self, steps: int = None, generator: torch.Generator = None,
                                        step_generator: torch.Generator = None, eta: float = 0, noise: torch.Tensor = None,
                                        encoding: torch.Tensor = None, guidance_scale: float = None,
-                                       negative_encoding: torch.Tensor = None, device_noise_seed: int = None
-                                       ) -> Tuple[Image.Image, Tuple[int, np.ndarray]]:
+                                       negative_encoding: torch.Tensor = None, device_noise_seed: int = None,
+                                       guidance_rescale: float = 0.0) -> Tuple[Image.Image, Tuple[int, np.ndarray]]:
         """Unconditional (or `encoding`-conditioned) sample from noise (`__init__.py:35-68`). `guidance_scale` > 1 and
-        `negative_encoding`: classifier-free guidance, `device_noise_seed`: all noise drawn on the device from its own counter-based
-        stream, both as `AudioDiffusionPipeline.__call__` documents them."""
+        `negative_encoding`: classifier-free guidance, `guidance_rescale`: its rescaled form (Lin et al. 2023 §3.4), `device_noise_seed`:
+        all noise drawn on the device from its own counter-based stream, all as `AudioDiffusionPipeline.__call__` documents them."""
         return self._one(steps=steps, generator=generator, step_generator=step_generator, eta=eta, noise=noise,
                          encoding=encoding, guidance_scale=guidance_scale, negative_encoding=negative_encoding,
-                         device_noise_seed=device_noise_seed)
+                         device_noise_seed=device_noise_seed, guidance_rescale=guidance_rescale)
 
     def generate_spectrogram_and_audio_from_audio(self, audio_file: str = None, raw_audio: np.ndarray = None, slice: int = 0,
                                                   start_step: int = 0, steps: int = None, generator: torch.Generator = None,

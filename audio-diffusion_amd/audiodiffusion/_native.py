@@ -48,7 +48,7 @@ class SchedStepArgs(C.Structure):      # include/adm.h: adm_sched_step_args
         ("step_dev", C.c_void_p), ("step", C.c_int), ("mask", C.c_void_p), ("n_mask_steps", C.c_int), ("mask_start", C.c_int),
         ("mask_end", C.c_int), ("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("mode", C.c_int), ("prediction", C.c_int),
         ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float), ("max_value", C.c_float), ("scale", C.c_void_p), ("noise_source", C.c_int),
-        ("seed", C.c_uint64), ("row_offset", C.c_int),
+        ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float), ("rescale", C.c_void_p),
     ]
 
 
@@ -58,7 +58,7 @@ class SampleLoopArgs(C.Structure):     # include/adm.h: adm_sample_loop_args
         ("step_noise", C.c_void_p), ("mask", C.c_void_p), ("mask_start", C.c_int), ("mask_end", C.c_int), ("u8_out", C.c_void_p),
         ("use_graph", C.c_int), ("mode", C.c_int), ("prediction", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float),
         ("max_value", C.c_float), ("encoding_uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise_source", C.c_int),
-        ("seed", C.c_uint64), ("row_offset", C.c_int),
+        ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float),
     ]
 
 

@@ -39,15 +39,18 @@ def _rows(t, lo, hi, global_batch, name, broadcast=False):
 
 @torch.no_grad()
 def sample_sharded(pipe, global_batch, steps=None, seed=42, eta=0.0, gather=True, group=None, encoding=None, guidance_scale=None,
-                   negative_encoding=None, device_noise=False):
+                   negative_encoding=None, device_noise=False, guidance_rescale=0.0):
     """Returns (images_u8, local_slice): uint8 tensor (global_batch, H, W) on every rank when `gather`, else the
     local shard; `local_slice` = (lo, hi) rows owned by this rank. encoding and negative_encoding are GLOBAL tensors
     (global_batch, seq, dim), row-sliced per rank like the noise (negative_encoding may have a leading 1 instead: broadcast);
-    guidance_scale as in `AudioDiffusionPipeline.__call__`. The row counts are checked before any rank samples.
+    guidance_scale and guidance_rescale as in `AudioDiffusionPipeline.__call__`. The row counts are checked before any rank samples.
     device_noise: `seed` keys the device noise stream (`device_noise_seed=seed`, row offset = this rank's first row) instead of a CPU
     generator: other images than the default path for the same seed, the same bytes for any world size, and no global noise tensor."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
+    # the keyword rules on every rank, rows or not: all raise, or none (a rank without rows never reaches the loop that checks them)
+    from . import ops
+    ops.guidance_rescale_on(guidance_rescale, pipe._guided(guidance_scale, negative_encoding, encoding))
     steps = steps or pipe.get_default_steps()
     pipe.scheduler.set_timesteps(steps)
     ss = pipe.unet.sample_size
@@ -57,8 +60,8 @@ def sample_sharded(pipe, global_batch, steps=None, seed=42, eta=0.0, gather=True
     enc = _rows(encoding, lo, hi, global_batch, "encoding")          # (on every rank, rows or not: all raise, or none)
     neg = _rows(negative_encoding, lo, hi, global_batch, "negative_encoding", broadcast=True)
     if device_noise:
-        return _finish(_sample_device_noise(pipe, lo, hi, H, W, seed, eta, enc, guidance_scale, neg), lo, hi, global_batch, world, H, W,
-                       dev, gather, group)
+        return _finish(_sample_device_noise(pipe, lo, hi, H, W, seed, eta, enc, guidance_scale, neg, guidance_rescale), lo, hi,
+                       global_batch, world, H, W, dev, gather, group)
     rows = pipe.scheduler.coef_rows(eta)
     n_noise = sum(1 for r in rows if r["k_noise"] != 0.0)
     x, sn = global_noise((global_batch, pipe.unet.in_channels, H, W), seed, n_noise)
@@ -68,14 +71,14 @@ def sample_sharded(pipe, global_batch, steps=None, seed=42, eta=0.0, gather=True
         step_noise = [next(it)[lo:hi].to(dev) if r["k_noise"] != 0.0 else None for r in rows]
     if hi > lo:
         _, u8 = pipe._denoise(x[lo:hi].contiguous().to(dev), 0, eta, None, None, 0, 0, step_noise=step_noise,
-                              encoding=enc, guidance_scale=guidance_scale, negative_encoding=neg)
+                              encoding=enc, guidance_scale=guidance_scale, negative_encoding=neg, guidance_rescale=guidance_rescale)
         u8 = u8.reshape(hi - lo, H, W)
     else:      # more ranks than rows (global_batch < world * per): this rank owns nothing, and still takes part in the gather
         u8 = None
     return _finish(u8, lo, hi, global_batch, world, H, W, dev, gather, group)
 
 
-def _sample_device_noise(pipe, lo, hi, H, W, seed, eta, enc, guidance_scale, neg):
+def _sample_device_noise(pipe, lo, hi, H, W, seed, eta, enc, guidance_scale, neg, guidance_rescale=0.0):
     """This rank's rows [lo:hi] with every normal drawn on the device: the latent rows from `ops.randn(..., row_offset=lo, noise_stream=1)`,
     the step noise inside the step kernel. -> (hi - lo, H, W) uint8, or None for a rank without rows."""
     if hi <= lo:
@@ -83,7 +86,7 @@ def _sample_device_noise(pipe, lo, hi, H, W, seed, eta, enc, guidance_scale, neg
     from . import ops
     x = ops.randn((hi - lo, pipe.unet.in_channels, H, W), seed, row_offset=lo, t=0, noise_stream=1, device=pipe.device)
     _, u8 = pipe._denoise(x, 0, eta, None, None, 0, 0, encoding=enc, guidance_scale=guidance_scale, negative_encoding=neg,
-                          device_noise_seed=seed, device_noise_row_offset=lo)
+                          device_noise_seed=seed, device_noise_row_offset=lo, guidance_rescale=guidance_rescale)
     return u8.reshape(hi - lo, H, W)
 
 

@@ -45,6 +45,23 @@ def _guidance(eps, uncond, guidance_scale):
     return True
 
 
+def guidance_rescale_on(guidance_rescale, guided):
+    """The rule of `guidance_rescale` (include/adm.h "guidance rescale"): None or 0 is off; a value in (0, 1] needs active classifier-free
+    guidance (`guided`); anything else is refused. -> True when the rescaled form is to run."""
+    if guidance_rescale is None:
+        return False
+    phi = float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:       # (nan fails both comparisons)
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} must be in [0, 1]")
+    if phi == 0.0:
+        return False
+    if not guided:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} rescales the guided model output: it needs active classifier-free "
+                         f"guidance (the pipeline: guidance_scale > 1, a UNet2DConditionModel and an `encoding`; a step: `guidance_scale` "
+                         f"with the unconditional output)")
+    return True
+
+
 def _seed64(seed, name="seed"):
     """A noise-stream seed as the uint64 the C-ABI takes."""
     seed = int(seed)
@@ -66,16 +83,23 @@ def randn(shape, seed, row_offset=0, t=0, noise_stream=0, device=None):
 
 
 def _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out=None, u8_out=None, noise=None, mask=None,
-                mask_start=0, mask_end=0):
-    """The `adm_sched_step_args` (include/adm.h) of a plain step on x, eps: (B,C,H,W); the callers add their mode's fields."""
+                mask_start=0, mask_end=0, guidance_rescale=None, rescale_out=None):
+    """The `adm_sched_step_args` (include/adm.h) of a plain step on x, eps: (B,C,H,W); the callers add their mode's fields.
+    -> (the struct, the tensors it points to that the caller did not pass and that must outlive the native call)"""
     _f32(x), _f32(eps)
     B, Cc, H, W = x.shape
     a = N.SchedStepArgs(x=N.ptr(x), eps=N.ptr(eps), noise=N.ptr(noise), out=N.ptr(out), u8_out=N.ptr(u8_out), coef_table=N.ptr(coef_table),
                         step_dev=N.ptr(step_dev), step=int(step), mask=N.ptr(mask), n_mask_steps=mask.shape[1] if mask is not None else 0,
                         mask_start=int(mask_start), mask_end=int(mask_end), B=B, C=Cc, H=H, W=W, prediction=int(prediction))
-    if _guidance(eps, uncond, guidance_scale):
+    guided = _guidance(eps, uncond, guidance_scale)
+    if guided:
         a.eps_uncond, a.guidance_scale = N.ptr(uncond), float(guidance_scale)
-    return a
+    keep = None
+    if guidance_rescale_on(guidance_rescale, guided):
+        keep = torch.empty((B,), dtype=torch.float32, device=x.device) if rescale_out is None else _f32(rescale_out)
+        assert keep.shape == (B,) and keep.device == x.device
+        a.guidance_rescale, a.rescale = float(guidance_rescale), N.ptr(keep)
+    return a, keep
 
 
 def _set_threshold(a, ratio, max_value, scale):
@@ -85,13 +109,15 @@ def _set_threshold(a, ratio, max_value, scale):
 
 
 def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, out=None, prediction=0, uncond=None,
-                    guidance_scale=None):
+                    guidance_scale=None, guidance_rescale=None, rescale_out=None):
     """Per-sample dynamic threshold s_b = clamp(quantile(|x0_b|, ratio), 1, max_value) of x0 = (x - sqrt_beta*eps) / sqrt_alpha
     (csrc/k_sched.hip `sched_threshold_kernel`: an exact radix select on the device, equal to torch.quantile to the bit). -> (B,) fp32.
     prediction != 0: `eps` is the model output of a sample (1) or v_prediction (2) model and x0 is formed accordingly. uncond,
     guidance_scale: classifier-free guidance, `eps` is the conditional output and x0 is that of
-    o = uncond + guidance_scale * (eps - uncond). One native call (`adm_sched_threshold_ex`)."""
-    a = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale)
+    o = uncond + guidance_scale * (eps - uncond). guidance_rescale, rescale_out: as in sched_step (the statistics kernel runs first). One
+    native call (`adm_sched_threshold_ex`)."""
+    a, _keep = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, guidance_rescale=guidance_rescale,
+                           rescale_out=rescale_out)
     out = torch.empty((a.B,), dtype=torch.float32, device=x.device) if out is None else out
     _set_threshold(a, ratio, max_value, out)
     N.check(N.lib().adm_sched_threshold_ex(a, N.stream_for(x)))
@@ -99,7 +125,8 @@ def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, o
 
 
 def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
-               step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None, noise_seed=None, noise_row_offset=0):
+               step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None, noise_seed=None, noise_row_offset=0,
+               guidance_rescale=None, rescale_out=None):
     """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194), one native call (`adm_sched_step_ex`). x,eps: (B,C,H,W).
     threshold: None, or (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it
     instead of the static clamp (scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device scalar
@@ -107,11 +134,15 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
     table). uncond, guidance_scale: classifier-free guidance, `eps` is the conditional model output and the step uses
     o = uncond + guidance_scale * (eps - uncond), combined inside the kernel. noise_seed (instead of `noise`): a row with k_noise != 0
     draws its noise inside the kernel from "adm noise stream 1" — `randn(x.shape, noise_seed, noise_row_offset, t=the row's timestep)`
-    without the tensor; noise_row_offset is the global row of x[0]."""
+    without the tensor; noise_row_offset is the global row of x[0]. guidance_rescale (None or 0: off, the kernels of the unrescaled step):
+    phi in (0, 1] rescales the guided output per sample, o' = phi*(o*r_b) + (1 - phi)*o with r_b = std(eps_b) / std(o_b) computed on the
+    device first (include/adm.h "guidance rescale"; `guidance_stats_kernel`); needs uncond and guidance_scale. rescale_out: optional (B,)
+    fp32 that receives r_b."""
     if noise_seed is not None and noise is not None:
         raise ValueError("`noise_seed` (noise drawn inside the kernel) and `noise=` (a noise tensor) exclude each other")
     out = torch.empty_like(x) if out is None else out
-    a = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out, u8_out, noise, mask, mask_start, mask_end)
+    a, _keep = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out, u8_out, noise, mask, mask_start,
+                           mask_end, guidance_rescale, rescale_out)
     if threshold is not None:
         a.mode = N.SCHED_THRESH   # (`scale` is a local: the struct holds its address only, and it must outlive the call)
         scale = torch.empty((a.B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
@@ -123,15 +154,16 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
 
 
 def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
-                    u8_out=None, step_dev=None, uncond=None, guidance_scale=None):
+                    u8_out=None, step_dev=None, uncond=None, guidance_scale=None, guidance_rescale=None, rescale_out=None):
     """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP, ...>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,)
     fp32 beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev:
     optional int32 device scalar that replaces `step`. uncond, guidance_scale: classifier-free guidance as in sched_step; hist then
-    holds x0 of the guided output."""
+    holds x0 of the guided output. guidance_rescale, rescale_out: as in sched_step; hist then holds x0 of the rescaled output."""
     _f32(hist), _f32(k_hist_table)
     assert hist.shape == x.shape and k_hist_table.numel() == coef_table.shape[0]
     out = torch.empty_like(x) if out is None else out
-    a = _sched_args(x, eps, coef_table, step, step_dev, 0, uncond, guidance_scale, out, u8_out, noise, mask, mask_start, mask_end)
+    a, _keep = _sched_args(x, eps, coef_table, step, step_dev, 0, uncond, guidance_scale, out, u8_out, noise, mask, mask_start, mask_end,
+                           guidance_rescale, rescale_out)
     a.mode, a.k_hist_table, a.hist = N.SCHED_MULTISTEP, N.ptr(k_hist_table), N.ptr(hist)
     N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
     return out

@@ -202,18 +202,20 @@ class AudioDiffusionPipeline(DiffusionPipeline):
 
     def _denoise(self, images, start_step, eta, step_generator, mask, mask_start, mask_end, step_noise=None,
                  use_graph=True, want_u8=True, encoding=None, stop_step=None, guidance_scale=None, negative_encoding=None,
-                 device_noise_seed=None, device_noise_row_offset=0):
+                 device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=0.0):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
         before that step index, so that a single step of a long schedule can be compared in isolation.
         Every combination is one `adm_sample_loop_args` (include/adm.h) and one `adm_sample_loop_ex` call per chunk.
         guidance_scale > 1: every step is two forwards (the encoding, the negative encoding) and one guided step kernel, inside the
-        same native call; otherwise one forward per step.
+        same native call; otherwise one forward per step. guidance_rescale in (0, 1] (needs the guided loop): one statistics kernel more
+        per step, and the step uses the rescaled guided output (include/adm.h "guidance rescale").
         device_noise_seed: the noise of every noisy row is drawn inside the step kernel ("adm noise stream 1", include/adm.h) at (seed,
         device_noise_row_offset + b, the row's timestep): ONE native call whatever the number of steps, no staging tensor, no chunks,
         no synchronisation. A schedule without noisy rows (DDIM with eta == 0, the multistep solver) has nothing to draw."""
         sched, unet = self.scheduler, self.unet
         self._device_noise(device_noise_seed, step_generator=step_generator, step_noise=step_noise)
         guided = self._guided(guidance_scale, negative_encoding, encoding)
+        rescaled = ops.guidance_rescale_on(guidance_rescale, guided)
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
         thresh = None if multistep else sched.threshold()
         pred = 0 if multistep else sched.prediction   # the C-ABI's `prediction`; the multistep step is epsilon only
@@ -275,6 +277,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 args.lo, args.hi, args.w = ops.threshold_ranks(Cc * H * W, thresh[0])
             if guided:   # two forwards per step, the second on this encoding
                 args.encoding_uncond, args.guidance_scale = N.ptr(unet._enc_uncond), float(guidance_scale)
+            if rescaled:
+                args.guidance_rescale = float(guidance_rescale)
             if philox:   # noise drawn in the step kernel: no staging tensor
                 args.noise_source, args.row_offset = 1, int(device_noise_row_offset)
                 args.seed = ops._seed64(device_noise_seed, "device_noise_seed")
@@ -309,6 +313,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         negative_encoding=None,
         device_noise_seed: int = None,
         device_noise_row_offset: int = 0,
+        guidance_rescale: float = 0.0,
     ) -> Union[PipelineOutput, Tuple[List[Image.Image], Tuple[int, List[np.ndarray]]]]:
         """Generate random mel spectrogram from audio input and convert to audio (reference docstring `:89-112`).
 
@@ -325,6 +330,11 @@ class AudioDiffusionPipeline(DiffusionPipeline):
           * `negative_encoding` None means zeros of the encoding's shape (what `train_unet.py --encoding_dropout` trains the model
             to read as "no condition"); otherwise it must have the encoding's shape, a leading 1 being broadcast over the batch.
           * a `negative_encoding` without g > 1 is a ValueError.
+          * `guidance_rescale` phi (Lin et al. 2023 §3.4; diffusers' keyword): None or 0 is the guided path above, exactly. phi in (0, 1]
+            pulls the per-sample standard deviation of the guided output back towards that of the conditional one before every step,
+            o' = phi*(o*std(c)/std(o)) + (1 - phi)*o, computed on the device inside the captured loop (include/adm.h "guidance
+            rescale"). It needs active guidance (g > 1, a conditional model, an encoding): otherwise ValueError naming guidance_scale.
+            A value outside [0, 1] is a ValueError naming guidance_rescale.
 
         Device noise, off by default: `device_noise_seed` (an int in [0, 2^64)). All noise then comes from "adm noise stream 1"
         (include/adm.h): a counter-based generator evaluated on the device, a pure function of (seed, global sample row, timestep,
@@ -333,7 +343,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         `device_noise_row_offset` + b, so a sample's bits depend on neither its batch nor its shard. It is NOT torch.randn's stream: the
         same seed gives other images than a torch generator. With `generator`, `step_generator` or `step_noise` it is a ValueError; with
         the multistep scheduler (no noisy steps) the seed only picks the initial latent."""
-        self._guided(guidance_scale, negative_encoding, encoding)   # the ValueErrors, before any work
+        ops.guidance_rescale_on(guidance_rescale, self._guided(guidance_scale, negative_encoding, encoding))   # the ValueErrors, before any work
         self._device_noise(device_noise_seed, generator=generator, step_generator=step_generator, step_noise=step_noise)
         steps = steps or self.get_default_steps()
         self.scheduler.set_timesteps(steps)
@@ -383,7 +393,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         images, u8 = self._denoise(images, start_step, eta, step_generator, use_mask, mask_start, mask_end,
                                    step_noise=step_noise, want_u8=self.vqvae is None, encoding=encoding,
                                    guidance_scale=guidance_scale, negative_encoding=negative_encoding,
-                                   device_noise_seed=device_noise_seed, device_noise_row_offset=device_noise_row_offset)
+                                   device_noise_seed=device_noise_seed, device_noise_row_offset=device_noise_row_offset,
+                                   guidance_rescale=guidance_rescale)
 
         if self.vqvae is not None:
             # 0.18215 was scaling factor used in training to ensure unit variance (pipeline:187-190); the 1/0.18215

@@ -19,6 +19,8 @@ there, an epsilon scheduler refuses such a schedule. The multistep scheduler sta
 Classifier-free guidance: `step(..., model_output_uncond=u, guidance_scale=g)` of the three schedulers takes the conditional output as
 `model_output` and steps with u + g*(model_output - u), combined inside the one fused kernel (the struct's `eps_uncond`; the
 thresholded and the multistep paths included). Both keywords or neither; the `<= 1 means off` rule belongs to the pipeline.
+Guidance rescale (Lin et al. 2023 §3.4): `step(..., guidance_rescale=phi)` with the two keywords above rescales that combined output per
+sample towards the standard deviation of the conditional one before it is used (include/adm.h "guidance rescale"); None or 0 is off.
 Device noise: `step(..., device_noise_seed=s, device_noise_row_offset=r)` (DDPM, DDIM with eta > 0) draws the step's noise inside the fused
 kernel from "adm noise stream 1" (include/adm.h) at (seed s, global row r + b, the step's timestep) instead of `randn_tensor`
 (the struct's `noise_source` 1). Not together with `generator` or `variance_noise`.
@@ -251,7 +253,7 @@ class _SchedulerBase:
         return float(self.config.dynamic_thresholding_ratio), float(self.config.sample_max_value)
 
     def _step(self, model_output, timestep, sample, eta, generator, variance_noise, model_output_uncond=None, guidance_scale=None,
-              device_noise_seed=None, device_noise_row_offset=0):
+              device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=None):
         if device_noise_seed is not None:
             for name, given in (("generator", generator), ("variance_noise", variance_noise)):
                 if given is not None:
@@ -265,7 +267,8 @@ class _SchedulerBase:
                               noise=variance_noise.contiguous() if variance_noise is not None else None,
                               threshold=self.threshold(), prediction=self.prediction,
                               uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
-                              guidance_scale=guidance_scale, noise_seed=device_noise_seed, noise_row_offset=device_noise_row_offset)
+                              guidance_scale=guidance_scale, noise_seed=device_noise_seed, noise_row_offset=device_noise_row_offset,
+                              guidance_rescale=guidance_rescale)
         return SchedulerOutput(prev_sample=prev)
 
 
@@ -301,9 +304,9 @@ class DDPMScheduler(_SchedulerBase):
         return rows
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None, *,
-             model_output_uncond=None, guidance_scale=None, device_noise_seed=None, device_noise_row_offset=0):
+             model_output_uncond=None, guidance_scale=None, device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=None):
         return self._step(model_output, timestep, sample, 0.0, generator, variance_noise, model_output_uncond, guidance_scale,
-                          device_noise_seed, device_noise_row_offset)
+                          device_noise_seed, device_noise_row_offset, guidance_rescale)
 
 
 class DDIMScheduler(_SchedulerBase):
@@ -349,11 +352,11 @@ class DDIMScheduler(_SchedulerBase):
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True, *, model_output_uncond=None, guidance_scale=None, device_noise_seed=None,
-             device_noise_row_offset=0):
+             device_noise_row_offset=0, guidance_rescale=None):
         if use_clipped_model_output:
             raise NotImplementedError("use_clipped_model_output is not implemented (the reference never sets it)")
         return self._step(model_output, timestep, sample, float(eta), generator, variance_noise, model_output_uncond, guidance_scale,
-                          device_noise_seed, device_noise_row_offset)
+                          device_noise_seed, device_noise_row_offset, guidance_rescale)
 
 
 def _f32(v):
@@ -507,7 +510,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
 
     # ---- eager step ---------------------------------------------------------------------------------------
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, *,
-             model_output_uncond=None, guidance_scale=None):
+             model_output_uncond=None, guidance_scale=None, guidance_rescale=None):
         """One fused kernel (with model_output_uncond and guidance_scale: the guided one, whose history is x0 of the guided output). First order on the first call after `set_timesteps` (and whenever the call does not continue the
         previous one: another row than the next, another shape or device); the scheduler holds the history tensor."""
         i = self._index_of(timestep)
@@ -524,7 +527,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         table, khist = self._ms_tables[key]
         prev = ops.sched_multistep(sample.contiguous(), model_output.contiguous(), table, khist, self._hist, i,
                                    uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
-                                   guidance_scale=guidance_scale)
+                                   guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
         self._last_index = i
         if not return_dict:
             return (prev,)

@@ -17,6 +17,7 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
   int lo = 0, hi = 0; float w = 0.f, max_value = 1.f; float* scale = nullptr;   // SCHED_THRESH: ranks, weight, maximum; (B,) thresholds
   float* hist = nullptr; const float* k_hist_table = nullptr;                   // SCHED_MULTISTEP
   const float* eps_uncond = nullptr; float guidance = 1.f;   // classifier-free guidance: eps is the conditional output, o = u + g*(c - u)
+  float guidance_rescale = 0.f; float* rescale = nullptr;    // guidance rescale phi (0: off) and the (B,) factors r_b it writes and reads
   // the third noise source ("adm noise stream 1", include/adm.h), with noise == nullptr: {seed_lo, seed_hi, row_offset, stream id} read
   // from the device block nblock (the captured loop: the handle's, rewritten before every run) or, when it is null, from nvals
   int philox = 0; const uint32_t* nblock = nullptr; uint32_t nvals[4] = {0, 0, 0, 0};
@@ -25,7 +26,7 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
 int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, hipStream_t st);
 int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
 int launch_step_advance(int* step_dev, hipStream_t st);
-int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred = PRED_EPSILON);   // the selection alone: p.scale[b] = s_b
+int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred = PRED_EPSILON, const char* who = "sched_threshold");   // the selection alone: p.scale[b] = s_b
 int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

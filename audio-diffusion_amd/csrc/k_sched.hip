@@ -27,10 +27,28 @@
 //           instantiations without it compile without a line of the generator. In the captured loop the key, the row offset and the
 //           stream id are read from a 16-byte device block (p.nblock), as the step index is read from *step_dev, so a new seed or shard
 //           offset replays the same graph; the eager entry point passes them by value (p.nvals).
-// 26 instantiations are built: plain and thresholded for the three prediction types, guided or not, with the stream or not (24), and the
-// multistep step for epsilon, guided or not (it has no noise rows). The launchers look the kernel up in a table filled at compile time
-// (kStepKernels by (mode, pred, guided, philox), kThresholdKernels by (pred, guided)); a combination that is not built is an empty slot and
-// is refused.
+//   RESCALE guidance rescale (Lin et al. 2023 §3.4; the arithmetic is defined in include/adm.h), NOT a template parameter: a runtime branch
+//           inside the GUIDED instantiations on p.guidance_rescale != 0, a kernel argument and so uniform over the whole grid (no
+//           divergence: a scalar compare and branch per float4). o' = sched_rescaled(o, r_b, phi) stands wherever o stood, in the step body
+//           and in the selection's key, through that ONE helper. Why not a third value of GUIDED: it would double the 13 guided step and
+//           the 3 guided selection instantiations for four flops per element in kernels that are bound by their 16 - 32 B/elem of traffic,
+//           and the branch leaves the arithmetic of the unrescaled path untouched: sched_guided's three operations carry no contraction
+//           flag, so what follows them fuses (or not) exactly as before whether o arrives directly or through the branch. With the
+//           rescale on, the step reads 4 B more per SAMPLE (r_b), nothing more per element.
+//           r_b comes from guidance_stats_kernel, launched before the selection and the step on the same stream: 8 B/elem read (c and u,
+//           both just written by conv_out and L2 / Infinity-Cache resident), B floats written. One workgroup of 1024 lanes per sample,
+//           as sched_threshold_kernel and with its trick of loads issued before use (two float4 pairs per lane, 64 KiB in flight per
+//           workgroup): at 256 x 256 a sample is 512 KiB over the two buffers, 16 float4 pairs per lane, eight turns of the loop, ONE
+//           sweep where the selection makes three or four of 12 B/elem. B workgroups leave most of the chip idle at B = 1, but a split
+//           over several workgroups would need a second pass or a consumer that sums partials, for a sweep that is latency bound either
+//           way and far shorter than the two forwards it follows (measured, profiles/guidance_rescale.md: 5.0 us at 64 x 64, B = 1, where
+//           the selection beside it takes 10.3, and 9.2 us against 52.1 at 256 x 256, B = 16). The sums are fp64,
+//           combined in a fixed order (lane, wave butterfly, LDS, one lane): no atomics and no global scratch, so r_b depends on neither
+//           the batch, the order of execution nor earlier replays of a captured graph.
+// 26 step instantiations are built: plain and thresholded for the three prediction types, guided or not, with the stream or not (24), and
+// the multistep step for epsilon, guided or not (it has no noise rows); the 13 guided ones carry the rescaled form. The launchers look the
+// kernel up in a table filled at compile time (kStepKernels by (mode, pred, guided, philox), kThresholdKernels by (pred, guided)); a
+// combination that is not built is an empty slot and is refused.
 #include "adm_kernels.h"
 #include <array>
 #include <cmath>
@@ -69,6 +87,24 @@ __device__ __forceinline__ float sched_guided(float u, float c, float g) {
   const float d = c - u;
   const float gd = g * d;
   return u + gd;
+}
+
+// guidance rescale (include/adm.h): o' = phi*(o*r) + (1 - phi)*o with r the sample's std(c) / std(o) from guidance_stats_kernel. Three
+// products and one sum, each rounded on its own, and 1 - phi formed in fp32: plain operators under `fp contract(off)` for sched_guided's
+// reason. ONE helper for the step body and the selection's key, so that both see the same bits.
+__device__ __forceinline__ float sched_rescaled(float o, float r, float phi) {
+#pragma clang fp contract(off)
+  const float om = 1.f - phi;
+  const float a = o * r;
+  const float b = phi * a;
+  const float k = om * o;
+  return b + k;
+}
+__device__ __forceinline__ float4 sched_guided4(const float4& u, const float4& c, float g) {
+  return make_float4(sched_guided(u.x, c.x, g), sched_guided(u.y, c.y, g), sched_guided(u.z, c.z, g), sched_guided(u.w, c.w, g));
+}
+__device__ __forceinline__ float4 sched_rescaled4(const float4& o, float r, float phi) {
+  return make_float4(sched_rescaled(o.x, r, phi), sched_rescaled(o.y, r, phi), sched_rescaled(o.z, r, phi), sched_rescaled(o.w, r, phi));
 }
 
 // ---- "adm noise stream 1" (include/adm.h) -----------------------------------------------------------------------------------------
@@ -126,6 +162,7 @@ __device__ __forceinline__ unsigned pack_u8x4(float a, float b, float c, float d
 //                    (0 * NaN must not reach the output). Each lane reads and rewrites its own elements of hist.
 // PRED: what p.eps holds (the model output o); e below is sched_eps of it, the model output itself for PRED_EPSILON.
 // GUIDED: p.eps is the conditional output and o = sched_guided(p.eps_uncond, p.eps, p.guidance): in x0, in e and so in the history m0.
+//   With p.guidance_rescale != 0 (uniform over the grid) o is replaced by sched_rescaled(o, p.rescale[b], p.guidance_rescale).
 // PHILOX: the noise of a row with k_noise != 0 is noise_stream_normals of (q, row) = (i % (per_sample/4), row offset + i / (per_sample/4))
 // at the row's integer timestep, and p.noise is not read; a row with k_noise == 0 draws nothing (the branch is uniform over the grid).
 // out may alias x.
@@ -140,6 +177,7 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
   const bool use_noise = (PHILOX || p.noise != nullptr) && c.k_noise != 0.f;
   uint32_t nk0 = 0, nk1 = 0, nrow0 = 0, nsid = 0, nt = 0;
   const long n4s = p.per_sample >> 2;   // float4 per sample
+  const bool rescaled = GUIDED && p.guidance_rescale != 0.f;
   if (PHILOX) {
     nk0 = p.nblock ? p.nblock[0] : p.nvals[0]; nk1 = p.nblock ? p.nblock[1] : p.nvals[1];
     nrow0 = p.nblock ? p.nblock[2] : p.nvals[2]; nsid = p.nblock ? p.nblock[3] : p.nvals[3];
@@ -150,15 +188,16 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
   for (long i = first; i < p.n4; i += stride) {
     const float4 xv = reinterpret_cast<const float4*>(p.x)[i];
     float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
+    long row = 0;   // the float4's sample: one division, shared by the rescale factor and the noise stream's counter
+    if (rescaled || (PHILOX && use_noise)) row = i / n4s;
     if (GUIDED) {
       const float4 uv = reinterpret_cast<const float4*>(p.eps_uncond)[i];
-      ev = make_float4(sched_guided(uv.x, ev.x, p.guidance), sched_guided(uv.y, ev.y, p.guidance), sched_guided(uv.z, ev.z, p.guidance),
-                       sched_guided(uv.w, ev.w, p.guidance));
+      ev = sched_guided4(uv, ev, p.guidance);
+      if (rescaled) ev = sched_rescaled4(ev, p.rescale[row], p.guidance_rescale);   // W % 4 == 0: a float4 never straddles two samples
     }
     float4 nv = make_float4(0.f, 0.f, 0.f, 0.f), hv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (PHILOX) {
       if (use_noise) {
-        const long row = i / n4s;
         nv = noise_stream_normals(nk0, nk1, (uint32_t)(i - row * n4s), nrow0 + (uint32_t)row, nt, nsid);
       }
     } else if (use_noise) nv = reinterpret_cast<const float4*>(noise)[i];
@@ -240,10 +279,11 @@ __device__ __forceinline__ float thresh_bits_to_float(unsigned u) {
 
 // One sweep of a sample: f(key) for the key of every element. Four float4 pairs (GUIDED: triples) per lane are loaded before any is used:
 // with one workgroup per sample (a single CU when B = 1) the sweep is bound by load latency, not by bandwidth.
-// GUIDED: up is the unconditional output and the key is |x0| of sched_guided(up, ep, g), the step body's own combination.
+// GUIDED: up is the unconditional output and the key is |x0| of sched_guided(up, ep, g), the step body's own combination; with phi != 0
+// (uniform over the workgroup) of sched_rescaled(that, r, phi), r the sample's rescale factor.
 template <int PRED, bool GUIDED, class F>
 __device__ __forceinline__ void thresh_sweep(const float4* __restrict__ xp, const float4* __restrict__ ep, const float4* __restrict__ up,
-                                             float g, int n4, int tid, const adm_sched_coef& c, F f) {
+                                             float g, float r, float phi, int n4, int tid, const adm_sched_coef& c, F f) {
   for (int i0 = tid; i0 < n4; i0 += 4 * kThreshThreads) {
     float4 xv[4], ev[4], uv[4];
     ADM_UNROLL
@@ -257,9 +297,10 @@ __device__ __forceinline__ void thresh_sweep(const float4* __restrict__ xp, cons
     ADM_UNROLL
     for (int u = 0; u < 4; ++u) {
       if (i0 + u * kThreshThreads < n4) {
-        if (GUIDED)
-          ev[u] = make_float4(sched_guided(uv[u].x, ev[u].x, g), sched_guided(uv[u].y, ev[u].y, g), sched_guided(uv[u].z, ev[u].z, g),
-                              sched_guided(uv[u].w, ev[u].w, g));
+        if (GUIDED) {
+          ev[u] = sched_guided4(uv[u], ev[u], g);
+          if (phi != 0.f) ev[u] = sched_rescaled4(ev[u], r, phi);
+        }
         f(thresh_key<PRED>(xv[u].x, ev[u].x, c)); f(thresh_key<PRED>(xv[u].y, ev[u].y, c));
         f(thresh_key<PRED>(xv[u].z, ev[u].z, c)); f(thresh_key<PRED>(xv[u].w, ev[u].w, c));
       }
@@ -291,7 +332,7 @@ __device__ __forceinline__ void thresh_find_bin(const unsigned* hist, int nbins,
 template <int PRED, bool GUIDED>
 __device__ __forceinline__ void sched_threshold_body(
     const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_uncond, float guidance,
-    const adm_sched_coef* __restrict__ table,
+    const float* __restrict__ rescale, float phi, const adm_sched_coef* __restrict__ table,
     const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w, float max_value,
     float* __restrict__ scale) {
   __shared__ unsigned hist[kThreshBins];
@@ -302,6 +343,8 @@ __device__ __forceinline__ void sched_threshold_body(
   const float4* uq = GUIDED ? reinterpret_cast<const float4*>(eps_uncond + (long)blockIdx.x * per_sample) : nullptr;
   const int n4 = (int)(per_sample >> 2);
   const int tid = threadIdx.x;
+  if (!GUIDED) phi = 0.f;
+  const float rs = phi != 0.f ? rescale[blockIdx.x] : 1.f;
   if (tid < 3) sel[tid] = 0;
   unsigned prefix = 0, k = lo, run = 0;
   for (int pass = 0; pass < 3; ++pass) {
@@ -310,7 +353,7 @@ __device__ __forceinline__ void sched_threshold_body(
     const int up = pass == 0 ? 31 : shift + 10;                // the digits above this one are fixed by `prefix`
     for (int j = tid; j < nbins; j += kThreshThreads) hist[j] = 0;
     __syncthreads();
-    thresh_sweep<PRED, GUIDED>(xp, ep, uq, guidance, n4, tid, c, [&](unsigned key) {
+    thresh_sweep<PRED, GUIDED>(xp, ep, uq, guidance, rs, phi, n4, tid, c, [&](unsigned key) {
       if ((key >> up) == (prefix >> up)) atomicAdd(&hist[(key >> shift) & (unsigned)(nbins - 1)], 1u);
     });
     __syncthreads();
@@ -326,7 +369,7 @@ __device__ __forceinline__ void sched_threshold_body(
     if (tid == 0) hist[0] = 0;
     __syncthreads();
     unsigned m = 0xffffffffu;
-    thresh_sweep<PRED, GUIDED>(xp, ep, uq, guidance, n4, tid, c, [&](unsigned key) {
+    thresh_sweep<PRED, GUIDED>(xp, ep, uq, guidance, rs, phi, n4, tid, c, [&](unsigned key) {
       if (key > prefix && key < m) m = key;
     });
     for (int d = 32; d >= 1; d >>= 1) {
@@ -348,13 +391,74 @@ __device__ __forceinline__ void sched_threshold_body(
   }
 }
 
-// One signature for the six instantiations; the unguided ones ignore eps_uncond and guidance, as the body does.
+// One signature for the six instantiations; the unguided ones ignore eps_uncond, guidance, rescale and phi, as the body does.
 template <int PRED, bool GUIDED>
 __global__ void __launch_bounds__(kThreshThreads) sched_threshold_kernel(
     const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_uncond, float guidance,
-    const adm_sched_coef* __restrict__ table, const int* __restrict__ step_dev, int step, long per_sample, unsigned lo, unsigned hi, float w,
-    float max_value, float* __restrict__ scale) {
-  sched_threshold_body<PRED, GUIDED>(x, eps, eps_uncond, guidance, table, step_dev, step, per_sample, lo, hi, w, max_value, scale);
+    const float* __restrict__ rescale, float phi, const adm_sched_coef* __restrict__ table, const int* __restrict__ step_dev, int step,
+    long per_sample, unsigned lo, unsigned hi, float w, float max_value, float* __restrict__ scale) {
+  sched_threshold_body<PRED, GUIDED>(x, eps, eps_uncond, guidance, rescale, phi, table, step_dev, step, per_sample, lo, hi, w, max_value,
+                                     scale);
+}
+
+// ---- guidance rescale: the per-sample factor r_b = std(c_b) / std(o_b) (include/adm.h) ---------------------------------------------------
+// One workgroup per sample. Both standard deviations come from one sweep of fp64 sums of d and d*d, d = v - v[first element of the sample]:
+// the shift by the sample's own first element makes a constant sample give 0 exactly (every d is 0) and takes the mean out of the
+// cancellation in S2 - S1*S1/n, and it depends on the sample alone. d is exact in fp64 unless the two exponents lie more than 29 binades
+// apart, and then off by 2^-53 relative. The eight partial sums are combined in a fixed order: the lane's own elements in index order,
+// a __shfl_xor butterfly over the wave, one LDS slot per wave, and lane 0 adding the 16 slots in wave order. No atomics, no global scratch.
+constexpr int kStatsThreads = 1024, kStatsLoads = 2;   // float4 pairs (c, u) in flight per lane: 64 KiB per workgroup
+
+__global__ void __launch_bounds__(kStatsThreads) guidance_stats_kernel(const float* __restrict__ eps, const float* __restrict__ eps_uncond,
+                                                                       float g, long per_sample, float* __restrict__ rescale) {
+  __shared__ double red[4][kStatsThreads / 64];
+  const float4* cp = reinterpret_cast<const float4*>(eps + (long)blockIdx.x * per_sample);
+  const float4* up = reinterpret_cast<const float4*>(eps_uncond + (long)blockIdx.x * per_sample);
+  const int n4 = (int)(per_sample >> 2);
+  const int tid = threadIdx.x;
+  const float c0 = eps[(long)blockIdx.x * per_sample];
+  const float o0 = sched_guided(eps_uncond[(long)blockIdx.x * per_sample], c0, g);
+  double s[4] = {0.0, 0.0, 0.0, 0.0};   // sum dc, sum dc^2, sum do, sum do^2
+  auto add = [&](float c, float u) {
+    const double dc = (double)c - (double)c0, dv = (double)sched_guided(u, c, g) - (double)o0;
+    s[0] += dc; s[1] += dc * dc; s[2] += dv; s[3] += dv * dv;
+  };
+  for (int i0 = tid; i0 < n4; i0 += kStatsLoads * kStatsThreads) {
+    float4 cv[kStatsLoads], uv[kStatsLoads];
+    ADM_UNROLL
+    for (int k = 0; k < kStatsLoads; ++k) {
+      const int i = i0 + k * kStatsThreads;
+      if (i < n4) { cv[k] = cp[i]; uv[k] = up[i]; }
+    }
+    ADM_UNROLL
+    for (int k = 0; k < kStatsLoads; ++k) {
+      if (i0 + k * kStatsThreads < n4) {
+        add(cv[k].x, uv[k].x); add(cv[k].y, uv[k].y); add(cv[k].z, uv[k].z); add(cv[k].w, uv[k].w);
+      }
+    }
+  }
+  ADM_UNROLL
+  for (int j = 0; j < 4; ++j)
+    for (int m = 32; m >= 1; m >>= 1) s[j] += __shfl_xor(s[j], m, 64);
+  if ((tid & 63) == 0) {
+    ADM_UNROLL
+    for (int j = 0; j < 4; ++j) red[j][tid >> 6] = s[j];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double t[4];
+    ADM_UNROLL
+    for (int j = 0; j < 4; ++j) {
+      t[j] = red[j][0];
+      for (int wv = 1; wv < kStatsThreads / 64; ++wv) t[j] += red[j][wv];
+    }
+    const double n = (double)per_sample;
+    const double var_c = (t[1] - t[0] * t[0] / n) / (n - 1.0), var_o = (t[3] - t[2] * t[2] / n) / (n - 1.0);   // unbiased, as torch.std
+    const float std_c = (float)sqrt(var_c > 0.0 ? var_c : (var_c == var_c ? 0.0 : var_c));   // (a rounding below zero is zero; NaN stays)
+    const float std_o = (float)sqrt(var_o > 0.0 ? var_o : (var_o == var_o ? 0.0 : var_o));
+    const bool ok = std_o != 0.f && std_c - std_c == 0.f && std_o - std_o == 0.f;   // x - x == 0: x is finite
+    rescale[blockIdx.x] = ok ? __fdiv_rn(std_c, std_o) : 1.f;
+  }
 }
 
 __global__ void step_advance_kernel(int* step_dev) { *step_dev += 1; }
@@ -431,8 +535,8 @@ static inline int ew_grid(long n4) {
 // The kernel tables. A slot is a kernel's address, or nullptr for a combination that is not built: the helper keeps those from being
 // instantiated (their static_asserts would fire).
 using StepKernel = void (*)(const SchedStepParams);
-using ThresholdKernel = void (*)(const float*, const float*, const float*, float, const adm_sched_coef*, const int*, int, long, unsigned,
-                                 unsigned, float, float, float*);
+using ThresholdKernel = void (*)(const float*, const float*, const float*, float, const float*, float, const adm_sched_coef*, const int*,
+                                 int, long, unsigned, unsigned, float, float, float*);
 
 template <int MODE, int PRED, bool GUIDED, bool PHILOX>
 constexpr StepKernel step_kernel_or_null() {
@@ -455,8 +559,24 @@ static constexpr auto kStepKernels = step_kernel_table(std::make_index_sequence<
 static constexpr auto kThresholdKernels = threshold_kernel_table(std::make_index_sequence<3 * 2>{});
 static_assert(step_slot(SCHED_MULTISTEP, PRED_V, true, true) == 35 && threshold_slot(PRED_V, true) == 5, "slot functions and tables agree");
 
-// reads p's x, eps, eps_uncond, guidance, table, step_dev, step, the ranks and the shape; writes the B thresholds to p.scale
-int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred) {
+// guidance rescale on (p.guidance_rescale != 0): writes the B factors r_b to p.rescale; before the selection and the step, on their stream
+static int launch_guidance_stats(const SchedStepParams& p, hipStream_t st, const char* who) {
+  const long per_sample = (long)p.C * p.H * p.W;
+  ADM_REQUIRE(std::isfinite(p.guidance_rescale) && p.guidance_rescale >= 0.f && p.guidance_rescale <= 1.f,
+              std::string(who) + ": guidance_rescale must be in [0, 1]");
+  if (p.guidance_rescale == 0.f) return 0;
+  ADM_REQUIRE(p.eps_uncond != nullptr, std::string(who) + ": guidance_rescale needs eps_uncond (it rescales the guided output)");
+  ADM_REQUIRE(p.rescale != nullptr, std::string(who) + ": guidance_rescale needs the rescale buffer");
+  ADM_REQUIRE(std::isfinite(p.guidance), std::string(who) + ": the guidance scale must be finite");
+  ADM_REQUIRE(p.B > 0 && p.W % 4 == 0, std::string(who) + ": W must be a multiple of 4");
+  ADM_REQUIRE(per_sample > 0 && per_sample < (1L << 31), std::string(who) + ": C*H*W must be below 2^31");
+  ADM_LAUNCH(guidance_stats_kernel, dim3(p.B), dim3(kStatsThreads), 0, st, p.eps, p.eps_uncond, p.guidance, per_sample, p.rescale);
+  return ADM_CHECK_LAUNCH();
+}
+
+// reads p's x, eps, eps_uncond, guidance, guidance_rescale, table, step_dev, step, the ranks and the shape; writes the B thresholds to
+// p.scale (and, with guidance_rescale != 0, the B factors to p.rescale first)
+int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred, const char* who) {
   const long per_sample = (long)p.C * p.H * p.W;
   const bool guided = p.eps_uncond != nullptr;
   ADM_REQUIRE(p.B > 0 && p.W % 4 == 0, "sched_threshold: W must be a multiple of 4");
@@ -467,9 +587,10 @@ int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred) {
   ADM_REQUIRE(p.max_value >= 1.f, "sched_threshold: max_value must be >= 1");
   ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_threshold: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
   if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_threshold: the guidance scale must be finite");
+  ADM_TRY(launch_guidance_stats(p, st, who));   // (its refusals carry the entry point's name: the thresholded step passes its own)
   const ThresholdKernel kernel = kThresholdKernels[threshold_slot(pred, guided)];
-  ADM_LAUNCH(kernel, dim3(p.B), dim3(kThreshThreads), 0, st, p.x, p.eps, p.eps_uncond, p.guidance, p.table, p.step_dev, p.step, per_sample,
-             (unsigned)p.lo, (unsigned)p.hi, p.w, p.max_value, p.scale);
+  ADM_LAUNCH(kernel, dim3(p.B), dim3(kThreshThreads), 0, st, p.x, p.eps, p.eps_uncond, p.guidance, p.rescale, p.guidance_rescale, p.table,
+             p.step_dev, p.step, per_sample, (unsigned)p.lo, (unsigned)p.hi, p.w, p.max_value, p.scale);
   return ADM_CHECK_LAUNCH();
 }
 
@@ -487,7 +608,8 @@ int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offs
   return ADM_CHECK_LAUNCH();
 }
 
-// SCHED_THRESH: selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written
+// SCHED_THRESH: selection, then the step on the same stream: the selection has read x before an `out` that aliases x is written.
+// guidance_rescale != 0: the statistics first (inside launch_sched_threshold for SCHED_THRESH), so statistics, selection, step.
 int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int pred) {
   ADM_REQUIRE(mode >= SCHED_PLAIN && mode <= SCHED_MULTISTEP, "sched_step: mode must be 0 (plain), 1 (thresholded) or 2 (multistep)");
   ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "sched_step: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
@@ -509,7 +631,8 @@ int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int p
     ADM_REQUIRE(pred == PRED_EPSILON, "sched_step: prediction must be 0 (the multistep step is epsilon only)");
     ADM_FAIL("sched_step: the multistep step has no noise rows");
   }
-  if (mode == SCHED_THRESH) ADM_TRY(launch_sched_threshold(p, st, pred));
+  if (mode == SCHED_THRESH) ADM_TRY(launch_sched_threshold(p, st, pred, "sched_step"));
+  else ADM_TRY(launch_guidance_stats(p, st, "sched_step"));
   ADM_LAUNCH(kernel, dim3(ew_grid(p.n4)), dim3(256), 0, st, p);
   return ADM_CHECK_LAUNCH();
 }

@@ -38,6 +38,7 @@ struct adm_unet {
   float *emb = nullptr, *emb_act = nullptr, *temb_all = nullptr, *t_dev = nullptr, *eps_buf = nullptr;
   float* hist_buf = nullptr;     // x0 of the previous step (multistep scheduler loop); same size as eps_buf
   float* scale_buf = nullptr;    // per-sample dynamic threshold of the thresholded loop (B floats)
+  float* rescale_buf = nullptr;  // per-sample guidance-rescale factor r_b of the rescaled guided loop (B floats)
   float* eps_uncond_buf = nullptr;   // the unconditional forward's output of a guided loop; same size as eps_buf, allocated with the
                                      // plan by the first guided loop at this batch size (free_plan releases it with the other extras)
   adm_sched_coef* coef_dev = nullptr;
@@ -296,6 +297,7 @@ static int plan(adm_unet* h, int B) {
   ADM_TRY(extra_alloc(h, (void**)&h->hist_buf,
                       sizeof(float) * (size_t)B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
   ADM_TRY(extra_alloc(h, (void**)&h->scale_buf, sizeof(float) * (size_t)B));
+  ADM_TRY(extra_alloc(h, (void**)&h->rescale_buf, sizeof(float) * (size_t)B));
   ADM_TRY(extra_alloc(h, (void**)&h->step_dev, sizeof(int)));
   if (h->training) {
     ADM_TRY(extra_alloc(h, (void**)&h->dtemb_all, sizeof(float) * (size_t)B * h->temb_rows));
@@ -383,7 +385,10 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
     p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
     p.lo = a.lo; p.hi = a.hi; p.w = a.w; p.max_value = a.max_value; p.scale = h->scale_buf;
     p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
-    if (a.encoding_uncond != nullptr) { p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance_scale; }
+    if (a.encoding_uncond != nullptr) {
+      p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance_scale;
+      p.guidance_rescale = a.guidance_rescale; p.rescale = h->rescale_buf;   // (0: off, the buffer is not touched)
+    }
     if (a.noise_source == 1) { p.philox = 1; p.nblock = h->noise_blk_dev; }
     ADM_TRY(launch_sched_step(p, a.mode, st, a.prediction));
   }
@@ -438,6 +443,11 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
       uint32_t gb;
       memcpy(&gb, &a.guidance_scale, 4);
       key.push_back((uint64_t)a.encoding_uncond); key.push_back((uint64_t)h->eps_uncond_buf); key.push_back(0x100000000ull | gb);
+      if (a.guidance_rescale != 0.f) {   // one more captured node (the statistics kernel), phi a kernel argument of the step and the selection
+        uint32_t rb;
+        memcpy(&rb, &a.guidance_rescale, 4);
+        key.push_back(0x300000000ull | rb); key.push_back((uint64_t)h->rescale_buf);
+      }
     }
     // the noise stream: the block's address (the handle's, stable) and nothing else; the seed and the row offset are data behind it
     if (a.noise_source == 1) { key.push_back(0x200000000ull); key.push_back((uint64_t)h->noise_blk_dev); }
@@ -724,6 +734,10 @@ int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* strea
     ADM_REQUIRE(h->net.ctx != nullptr && h->net.ctx_S > 0, "sample_loop: no encoding set (adm_unet_set_encoding)");
     ADM_REQUIRE(std::isfinite(a->guidance_scale), "sample_loop: the guidance scale must be finite");
   }
+  ADM_REQUIRE(std::isfinite(a->guidance_rescale) && a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f,
+              "sample_loop: guidance_rescale must be in [0, 1]");
+  ADM_REQUIRE(a->guidance_rescale == 0.f || a->encoding_uncond != nullptr,
+              "sample_loop: guidance_rescale needs encoding_uncond (it rescales the guided output)");
   ADM_REQUIRE(a->prediction >= PRED_EPSILON && a->prediction <= PRED_V, "sample_loop: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
   if (a->mode == SCHED_MULTISTEP) {
     ADM_REQUIRE(a->k_hist_host != nullptr, "sample_loop: the multistep loop needs k_hist_host");

@@ -284,6 +284,8 @@ def write_samples(pipeline, args, epoch, output_dir, dev, encodings):
     n = args.eval_batch_size if encoding is None else encoding.shape[0]
     pipeline.set_progress_bar_config(disable=True)
     guide = {} if args.guidance_scale is None else {"guidance_scale": args.guidance_scale}   # unset: the call of before
+    if args.guidance_rescale is not None:
+        guide["guidance_rescale"] = args.guidance_rescale
     images, (sample_rate, audios) = pipeline(generator=generator, batch_size=n, return_dict=False, encoding=encoding, **guide)
     d = os.path.join(output_dir, "samples")
     os.makedirs(d, exist_ok=True)
@@ -336,6 +338,9 @@ def parse_args(argv=None):
                              "unconditional branch that classifier-free guidance (guidance_scale > 1) samples against")
     parser.add_argument("--guidance_scale", type=float, default=None,
                         help="guidance scale of the sample images written during training (unset: unguided)")
+    parser.add_argument("--guidance_rescale", type=float, default=None,
+                        help="guidance rescale (Lin et al. 2023, in (0, 1]; needs --guidance_scale > 1) of the sample images written "
+                             "during training (unset: not rescaled)")
     # additions (not in the reference)
     parser.add_argument("--resolution", type=int, default=256, help="image size of the synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=2048)

@@ -269,11 +269,33 @@ typedef struct adm_sched_step_args {
   int noise_source;          /* 0: `noise` (or none); 1: "adm noise stream 1", stream 0, drawn in the kernel from (seed, row_offset + b) */
   uint64_t seed;
   int row_offset;            /* noise_source 1: >= 0 and row_offset + B within 32 bits */
+  float guidance_rescale;    /* adm_version() >= 115. 0: off; otherwise phi in (0, 1], and needs eps_uncond and rescale ("guidance rescale" below) */
+  float* rescale;            /* (B,) device, caller-owned: receives r_b, as scale receives s_b */
 } adm_sched_step_args;
 int adm_sched_step_ex(const adm_sched_step_args* a, void* stream);
 /* The selection alone (adm_sched_threshold and its _pred / _guided forms): reads x, eps, eps_uncond, guidance_scale, coef_table, step_dev,
- * step, B, C, H, W, prediction, lo, hi, w, max_value of the same struct and writes scale; the other fields are ignored. */
+ * step, B, C, H, W, prediction, lo, hi, w, max_value, guidance_rescale of the same struct and writes scale (and, with guidance_rescale != 0,
+ * rescale first); the other fields are ignored. */
 int adm_sched_threshold_ex(const adm_sched_step_args* a, void* stream);
+
+/* Guidance rescale (adm_version() >= 115): Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4;
+ * diffusers' `rescale_noise_cfg` / `guidance_rescale` [3P-recall: restated from memory, diffusers is not consulted]. THE definition; the
+ * kernels (csrc/k_sched.hip) and the documents refer to it. Per sample b, with c the conditional model output, u the unconditional one, g
+ * the guidance scale, phi the fp32 guidance_rescale and n = C*H*W elements:
+ *   o      = u + g*(c - u)                                   unchanged: three separately rounded fp32 operations
+ *   std_c  = fp32( sqrt( sum((c - mean c)^2) / (n - 1) ) )   unbiased, as torch.std; the sums are accumulated in fp64, over
+ *   std_o  = fp32( sqrt( sum((o - mean o)^2) / (n - 1) ) )   d = v - v[first element of the sample] (S2 - S1*S1/n), in a fixed order
+ *   r_b    = std_c / std_o                                   one fp32 division
+ *            r_b = 1 when std_o == 0 or either standard deviation is not finite (n == 1 included).
+ *            Deliberate deviation: diffusers yields NaN there. A sample whose c and u are constant is left as guidance made it.
+ *   o'     = phi*(o*r_b) + (1 - phi)*o                       three products and one sum, each rounded on its own; 1 - phi formed in fp32
+ * o' stands wherever o stood: in x0, in e, in the multistep history and in the key of the thresholding selection. The rescale acts on the
+ * model output whatever it predicts (epsilon, sample or v). r_b is a function of sample b's c and u alone: it depends on neither the batch
+ * nor the order of execution (no floating-point atomics, no scratch that outlives a launch). With guidance_rescale != 0 the step entry
+ * points enqueue, on the one stream: the statistics kernel (8 B/elem read, writes rescale), the selection (mode 1), the step.
+ * guidance_rescale == 0 is the path of version 114, bit for bit, and the statistics kernel is not launched. Refused: a guidance_rescale
+ * outside [0, 1] or not finite; guidance_rescale != 0 with eps_uncond == NULL (encoding_uncond == NULL for the loop); guidance_rescale != 0
+ * with rescale == NULL (adm_sched_step_ex, adm_sched_threshold_ex; the loop's buffer is the handle's). */
 
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
@@ -597,6 +619,7 @@ typedef struct adm_sample_loop_args {
   int noise_source;
   uint64_t seed;
   int row_offset;
+  float guidance_rescale;    /* adm_version() >= 115: "guidance rescale" above; 0: off; otherwise needs encoding_uncond */
 } adm_sample_loop_args;
 int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
