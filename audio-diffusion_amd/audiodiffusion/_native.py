@@ -21,6 +21,10 @@ class SchedCoef(C.Structure):
                 ("sqrt_beta", "sqrt_alpha", "clip", "k_x0", "k_x", "k_eps", "k_noise", "timestep")]
 
 
+class SchedUnipcCoef(C.Structure):     # include/adm.h: adm_unipc_coef (one per row of the coefficient table; "UniPC")
+    _fields_ = [(n, C.c_float) for n in ("c_x", "c_m1", "c_m2", "c_t", "p_m1")]
+
+
 class ConvArgs(C.Structure):
     _fields_ = [
         ("x1", C.c_void_p), ("C1", C.c_int),
@@ -49,6 +53,7 @@ class SchedStepArgs(C.Structure):      # include/adm.h: adm_sched_step_args
         ("mask_end", C.c_int), ("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("mode", C.c_int), ("prediction", C.c_int),
         ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float), ("max_value", C.c_float), ("scale", C.c_void_p), ("noise_source", C.c_int),
         ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float), ("rescale", C.c_void_p),
+        ("unipc_table", C.c_void_p), ("last", C.c_void_p),
     ]
 
 
@@ -58,7 +63,7 @@ class SampleLoopArgs(C.Structure):     # include/adm.h: adm_sample_loop_args
         ("step_noise", C.c_void_p), ("mask", C.c_void_p), ("mask_start", C.c_int), ("mask_end", C.c_int), ("u8_out", C.c_void_p),
         ("use_graph", C.c_int), ("mode", C.c_int), ("prediction", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float),
         ("max_value", C.c_float), ("encoding_uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise_source", C.c_int),
-        ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float),
+        ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float), ("unipc_host", C.POINTER(SchedUnipcCoef)),
     ]
 
 

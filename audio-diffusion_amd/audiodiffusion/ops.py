@@ -169,6 +169,38 @@ def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, ma
     return out
 
 
+UNIPC_FIELDS = ("c_x", "c_m1", "c_m2", "c_t", "p_m1")   # include/adm.h: adm_unipc_coef
+
+
+def sched_unipc_table(rows, device):
+    """rows: list of dicts with the 5 adm_unipc_coef fields (beside the 8 of sched_coef_table) -> (n,5) fp32 device tensor."""
+    return torch.tensor([[float(r[k]) for k in UNIPC_FIELDS] for r in rows], dtype=torch.float32).to(device)
+
+
+def sched_unipc(x, eps, coef_table, unipc_table, hist, last, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
+                u8_out=None, step_dev=None, uncond=None, guidance_scale=None, guidance_rescale=None, rescale_out=None, threshold=None,
+                prediction=0, scale_out=None):
+    """Fused UniPC predictor-corrector step (csrc/k_unipc.hip `unipc_step_kernel`; include/adm.h "UniPC"), one native call
+    (`adm_sched_step_ex` with `unipc_table`). x, eps, last: (B,C,H,W); hist: (2,B,C,H,W); unipc_table: (n,5) fp32 beside the (n,8)
+    coef_table. Row `step` corrects x with the data predictions of this and the two previous rows (where its c_t != 0; `last` is read only
+    then), writes the corrected sample to `last` and this row's data prediction to hist[step & 1], and returns the predicted sample of
+    the next level. threshold, prediction, uncond, guidance_scale, guidance_rescale, rescale_out, scale_out, step_dev, mask: as in
+    sched_step; the history then holds x0 of the guided / rescaled / thresholded output. `noise` exists for the keyword set of
+    sched_multistep and must be None: the step has no noise rows (the native call refuses it by name)."""
+    _f32(hist), _f32(last), _f32(unipc_table)
+    assert tuple(hist.shape) == (2,) + tuple(x.shape) and last.shape == x.shape and unipc_table.shape == (coef_table.shape[0], 5)
+    out = torch.empty_like(x) if out is None else out
+    a, _keep = _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out, u8_out, noise, mask, mask_start,
+                           mask_end, guidance_rescale, rescale_out)
+    a.unipc_table, a.hist, a.last = N.ptr(unipc_table), N.ptr(hist), N.ptr(last)
+    if threshold is not None:
+        a.mode = N.SCHED_THRESH
+        scale = torch.empty((a.B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+        _set_threshold(a, threshold[0], threshold[1], scale)
+    N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
+    return out
+
+
 def add_noise(x0, noise, sa, sb, per_sample):
     """scheduler.add_noise. per_sample=True: x0,noise (B,...) with sa,sb (B,) -> (B,...).
     per_sample=False (mask build, pipeline:157): x0 (1,H,W) broadcast, noise (B,1,H,W), sa,sb (n,) -> (B,n,H,W)."""

@@ -27,7 +27,7 @@ from PIL import Image
 from . import _native as N
 from . import ops
 from .mel import Mel
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, randn_tensor
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler, randn_tensor
 from .unet import UNet2DConditionModel, UNet2DModel
 from .vae import AutoencoderKL
 
@@ -39,7 +39,7 @@ class PipelineOutput(dict):
 
 _CLASSES = {"AutoencoderKL": AutoencoderKL, "UNet2DModel": UNet2DModel, "UNet2DConditionModel": UNet2DConditionModel,
             "DDIMScheduler": DDIMScheduler, "DDPMScheduler": DDPMScheduler,
-            "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler, "Mel": Mel}
+            "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler, "UniPCMultistepScheduler": UniPCMultistepScheduler, "Mel": Mel}
 
 
 class DiffusionPipeline:
@@ -134,7 +134,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         vqvae: AutoencoderKL for latent audio diffusion or None
         unet: UNet2DModel
         mel: Mel — transform audio <-> spectrogram
-        scheduler: DDIMScheduler, DDPMScheduler or DPMSolverMultistepScheduler
+        scheduler: DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler or UniPCMultistepScheduler
     """
 
     _optional_components = ["vqvae"]
@@ -146,7 +146,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         self.register_modules(unet=unet, scheduler=scheduler, mel=mel, vqvae=vqvae)
 
     def get_default_steps(self) -> int:
-        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+        if isinstance(self.scheduler, (DPMSolverMultistepScheduler, UniPCMultistepScheduler)):
             return 20   # (the reference's rule would say 1000: pointless for a solver built for few steps)
         return 50 if isinstance(self.scheduler, DDIMScheduler) else 1000
 
@@ -217,10 +217,11 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         guided = self._guided(guidance_scale, negative_encoding, encoding)
         rescaled = ops.guidance_rescale_on(guidance_rescale, guided)
         multistep = isinstance(sched, DPMSolverMultistepScheduler)
+        unipc = isinstance(sched, UniPCMultistepScheduler)   # its own step kernel: every prediction type, thresholded or not
         thresh = None if multistep else sched.threshold()
         pred = 0 if multistep else sched.prediction   # the C-ABI's `prediction`; the multistep step is epsilon only
-        # (a multistep run that starts late starts first order: its rows depend on where it starts, not only on the slice)
-        rows = sched.loop_rows(start_step, stop_step) if multistep else sched.coef_rows(eta)[start_step:stop_step]
+        # (a multistep or UniPC run that starts late starts first order: its rows depend on where it starts, not only on the slice)
+        rows = sched.loop_rows(start_step, stop_step) if multistep or unipc else sched.coef_rows(eta)[start_step:stop_step]
         n = len(rows)
         x = images.contiguous().clone()  # the reference never writes the loop state back into `noise`
         B, Cc, H, W = x.shape
@@ -265,14 +266,16 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 mask_chunk = mask[:, done:done + m].contiguous()
                 mask_ptr = N.ptr(mask_chunk)
             u8_ptr = N.ptr(u8) if (last and u8 is not None) else None
-            # one entry point for every combination; device noise and the multistep history both need all steps in this one call
-            assert m == n or not (philox or multistep)
+            # one entry point for every combination; device noise, the multistep history and the UniPC state all need all steps in this one call
+            assert m == n or not (philox or multistep or unipc)
             args = N.SampleLoopArgs(x=N.ptr(x), B=B, coef_host=coef, n_steps=m, step_noise=noise_ptr, mask=mask_ptr,
                                     mask_start=int(mask_start), mask_end=int(mask_end), u8_out=u8_ptr, use_graph=int(use_graph),
                                     prediction=pred, max_value=1.0, guidance_scale=1.0)
             if multistep:
                 args.mode, args.k_hist_host = N.SCHED_MULTISTEP, (C.c_float * m)(*[float(r["k_hist"]) for r in sub])
-            elif thresh is not None:   # dynamic thresholding: the statistic is over this tensor's C*H*W (the latent's, with a VAE)
+            if unipc:
+                args.unipc_host = (N.SchedUnipcCoef * m)(*[N.SchedUnipcCoef(*[float(r[k]) for k in ops.UNIPC_FIELDS]) for r in sub])
+            if not multistep and thresh is not None:   # dynamic thresholding: the statistic is over this tensor's C*H*W (the latent's, with a VAE)
                 args.mode, args.max_value = N.SCHED_THRESH, thresh[1]
                 args.lo, args.hi, args.w = ops.threshold_ranks(Cc * H * W, thresh[0])
             if guided:   # two forwards per step, the second on this encoding
@@ -342,7 +345,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         eta > 0) draws inside the fused step kernel, and the loop is one native call without a noise tensor. Sample b is global row
         `device_noise_row_offset` + b, so a sample's bits depend on neither its batch nor its shard. It is NOT torch.randn's stream: the
         same seed gives other images than a torch generator. With `generator`, `step_generator` or `step_noise` it is a ValueError; with
-        the multistep scheduler (no noisy steps) the seed only picks the initial latent."""
+        the multistep and UniPC schedulers (no noisy steps) the seed only picks the initial latent."""
         ops.guidance_rescale_on(guidance_rescale, self._guided(guidance_scale, negative_encoding, encoding))   # the ValueErrors, before any work
         self._device_noise(device_noise_seed, generator=generator, step_generator=step_generator, step_noise=step_noise)
         steps = steps or self.get_default_steps()

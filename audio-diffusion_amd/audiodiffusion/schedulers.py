@@ -1,4 +1,4 @@
-"""DDPMScheduler / DDIMScheduler / DPMSolverMultistepScheduler drop-ins (duck-typed members the reference pipeline calls).
+"""DDPMScheduler / DDIMScheduler / DPMSolverMultistepScheduler / UniPCMultistepScheduler drop-ins (duck-typed members the reference pipeline calls).
 
 Reference call sites: `audiodiffusion/pipeline_audio_diffusion.py:115,150,157,166-179,221-234`,
 `scripts/train_unet.py:161-164,250`. Host side (this file): the beta/alpha tables and the per-step scalar
@@ -16,6 +16,10 @@ of the noise. The coefficient rows do not change; the step and selection kernels
 `ops.noise_and_velocity` give the training target. With them come `timestep_spacing` "linspace" / "trailing" and
 `rescale_betas_zero_snr` (Lin et al. 2023), whose last training timestep has alphas_cumprod == 0: only the two new types can start
 there, an epsilon scheduler refuses such a schedule. The multistep scheduler stays epsilon-only.
+`UniPCMultistepScheduler` (UniPC, Zhao et al. 2023) is the few-step solver for everything above: the three prediction types, zero-SNR
+schedules, thresholding, guidance and its rescale, through its own fused step kernel (csrc/k_unipc.hip; `adm_sched_step_ex` with
+`unipc_table`, `adm_sample_loop_ex` with `unipc_host`). `unipc_rows` computes its coefficient rows from a list of noise levels; the
+definition is in include/adm.h ("UniPC").
 Classifier-free guidance: `step(..., model_output_uncond=u, guidance_scale=g)` of the three schedulers takes the conditional output as
 `model_output` and steps with u + g*(model_output - u), combined inside the one fused kernel (the struct's `eps_uncond`; the
 thresholded and the multistep paths included). Both keywords or neither; the `<= 1 means off` rule belongs to the pipeline.
@@ -364,6 +368,30 @@ def _f32(v):
     return float(np.float32(v))
 
 
+def _solver_timesteps(cfg, N):
+    """The N timesteps of the few-step solvers (DPM-Solver++ multistep, UniPC) for `timestep_spacing` linspace / leading / trailing, with
+    their ValueErrors: every row must move to a strictly lower noise level."""
+    T = cfg.num_train_timesteps
+    if N < 1 or N > T:
+        raise ValueError("num_inference_steps must be in [1, num_train_timesteps]")
+    spacing = cfg.timestep_spacing
+    if spacing == "linspace":
+        ts = np.linspace(0, T - 1, N + 1).round()[::-1][:-1]
+    elif spacing == "leading":
+        ts = (np.arange(0, N + 1) * (T // (N + 1))).round()[::-1][:-1] + cfg.steps_offset
+    else:
+        ts = np.arange(T, 0, -T / N).round() - 1
+    ts = ts.copy().astype(np.int64)
+    # every row must move to a lower noise level (h > 0): the second-order rows divide by h
+    if ts.max() >= T or ts.min() < 0 or (np.diff(ts) >= 0).any():
+        raise ValueError(f"{N} steps with timestep_spacing={spacing!r} over {T} training timesteps give repeated or out-of-range "
+                         f"timesteps; use fewer steps")
+    if cfg.final_sigmas_type == "sigma_min" and ts[-1] == 0:
+        raise ValueError(f"{N} steps with timestep_spacing={spacing!r} reach timestep 0 before the final row, which "
+                         f"final_sigmas_type='sigma_min' ends at; use fewer steps or final_sigmas_type='zero'")
+    return ts
+
+
 class DPMSolverMultistepScheduler(_SchedulerBase):
     """DPM-Solver++ multistep (Lu et al. 2022, "2M"): a first- or second-order data-prediction solver of the
     probability-flow ODE, for sampling an epsilon-model trained on the DDPM schedule in 15-25 steps.
@@ -428,24 +456,8 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self._ms_tables = {}       # (device, first row of the run) -> (coef table, k_hist table) on the device
 
     def set_timesteps(self, num_inference_steps, device=None):
-        T, N = self.config.num_train_timesteps, int(num_inference_steps)
-        if N < 1 or N > T:
-            raise ValueError("num_inference_steps must be in [1, num_train_timesteps]")
-        spacing = self.config.timestep_spacing
-        if spacing == "linspace":
-            ts = np.linspace(0, T - 1, N + 1).round()[::-1][:-1]
-        elif spacing == "leading":
-            ts = (np.arange(0, N + 1) * (T // (N + 1))).round()[::-1][:-1] + self.config.steps_offset
-        else:
-            ts = np.arange(T, 0, -T / N).round() - 1
-        ts = ts.copy().astype(np.int64)
-        # every row must move to a lower noise level (h > 0): the second-order rows divide by h
-        if ts.max() >= T or ts.min() < 0 or (np.diff(ts) >= 0).any():
-            raise ValueError(f"{N} steps with timestep_spacing={spacing!r} over {T} training timesteps give repeated or out-of-range "
-                             f"timesteps; use fewer steps")
-        if self.config.final_sigmas_type == "sigma_min" and ts[-1] == 0:
-            raise ValueError(f"{N} steps with timestep_spacing={spacing!r} reach timestep 0 before the final row, which "
-                             f"final_sigmas_type='sigma_min' ends at; use fewer steps or final_sigmas_type='zero'")
+        N = int(num_inference_steps)
+        ts = _solver_timesteps(self.config, N)
         self.num_inference_steps = N
         self.timesteps = torch.from_numpy(ts)
         self._table = None
@@ -528,6 +540,206 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         prev = ops.sched_multistep(sample.contiguous(), model_output.contiguous(), table, khist, self._hist, i,
                                    uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
                                    guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+        self._last_index = i
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
+# ---- UniPC (include/adm.h "UniPC" has THE definition; the names below are its names) -------------------------------------------------
+def _unipc_phi_b(h, solver_type, K):
+    """(phi, B, [b_1 .. b_K]) of a step h > 0; h = +inf (the previous level at zero SNR): phi = B = -1 and no vector."""
+    if math.isinf(h):
+        return -1.0, -1.0, []
+    hh = -h
+    phi = math.expm1(hh)
+    B = phi if solver_type == "bh2" else hh
+    g, f, b = phi / hh - 1.0, 1.0, []
+    for k in range(1, K + 1):
+        b.append(g * f / B)
+        f *= k + 1
+        g = g / hh - 1.0 / f
+    return phi, B, b
+
+
+def unipc_rows(levels, solver_order=2, solver_type="bh2", run_start=0, lower_order_final=True, disable_corrector=()):
+    """The N coefficient rows of a UniPC run over `levels` = [(alpha_i, sigma_i, lambda_i) for i in 0..N] (float64) that STARTS at row
+    `run_start`: a pure function of the level list, so that any grid can be given (the scheduler passes its own; the convergence tests
+    an analytic one). Each row: the eight `adm_sched_coef` fields (timestep = the row index; the scheduler overwrites it) and the five
+    `adm_unipc_coef` fields, computed in float64 and rounded to fp32 once. Rows before `run_start` are as in a run from row 0 (such a
+    run never reads them)."""
+    if solver_type not in ("bh1", "bh2"):
+        raise NotImplementedError(f"solver_type={solver_type!r} is not implemented (implemented: 'bh1', 'bh2')")
+    if solver_order not in (1, 2):
+        raise NotImplementedError(f"solver_order={solver_order!r} is not implemented (implemented: 1, 2)")
+    N = len(levels) - 1
+    off = set(int(i) for i in disable_corrector)
+    rows, p_prev = [], None
+    for i in range(N):
+        (a0, s0, l0), (a1, s1, l1) = levels[i], levels[i + 1]
+        start = run_start if i >= run_start else 0
+        p = min(solver_order, i - start + 1, N - i if lower_order_final else solver_order)
+        if p == 2 and math.isinf(levels[i - 1][2]):     # a zero-SNR level is never history
+            p = 1
+        # the corrector of the move i-1 -> i, of the order of that move's predictor
+        c_x = c_m1 = c_m2 = c_t = 0.0
+        if i > start and (i - 1) not in off:
+            am, sm, lm = levels[i - 1]
+            q = 1 if math.isinf(lm) else p_prev
+            h = l0 - lm
+            phi, B, b = _unipc_phi_b(h, solver_type, q)
+            c_x = s0 / sm
+            if q == 1:
+                rho_last = 0.5
+            else:
+                r1 = (levels[i - 2][2] - lm) / h
+                rho_1 = (b[0] - b[1]) / (1.0 - r1)      # [[1, 1], [r1, 1]] rho = b
+                rho_last = b[0] - rho_1
+                c_m2 = -a0 * B * rho_1 / r1
+            c_t = -a0 * B * rho_last
+            c_m1 = -a0 * phi - c_t - c_m2
+        # the predictor of the move i -> i+1
+        p_m1 = 0.0
+        if math.isinf(l1):                # sigma = 0: x' = m_i, written out
+            k_x, k_x0 = 0.0, 1.0
+        elif math.isinf(l0):              # from zero SNR (alpha_i = 0, sigma_i = 1): phi = B = -1
+            k_x, k_x0 = s1, a1
+        else:
+            h = l1 - l0
+            phi, B, _ = _unipc_phi_b(h, solver_type, 0)
+            k_x, k_x0 = s1 / s0, -a1 * phi
+            if p == 2:
+                r1 = (levels[i - 1][2] - l0) / h
+                p_m1 = -a1 * B * 0.5 / r1
+                k_x0 -= p_m1
+        rows.append(dict(sqrt_beta=_f32(s0), sqrt_alpha=_f32(a0), clip=-1.0, k_x0=_f32(k_x0), k_x=_f32(k_x), k_eps=0.0, k_noise=0.0,
+                         timestep=float(i), c_x=_f32(c_x), c_m1=_f32(c_m1), c_m2=_f32(c_m2), c_t=_f32(c_t), p_m1=_f32(p_m1)))
+        p_prev = p
+    return rows
+
+
+class UniPCMultistepScheduler(_SchedulerBase):
+    """UniPC (Zhao et al. 2023): a multistep predictor of order 1 or 2 in data-prediction form plus a corrector that re-does each move
+    once the model has been evaluated at its end, raising the order of accuracy by one at no extra model evaluation. For 10-20 step
+    sampling of epsilon, sample and v_prediction models, zero-terminal-SNR schedules and dynamically thresholded ones included, which
+    `DPMSolverMultistepScheduler` refuses.
+
+    [3P-recall] Config names and defaults follow diffusers' `UniPCMultistepScheduler` as recalled; the arithmetic is defined in
+    include/adm.h ("UniPC") and anchored independently in tests/test_unipc.py (order 1 without correctors is DDIM, order 2 without
+    correctors is DPM-Solver++ 2M midpoint, and the observed convergence orders on an analytic Gaussian model).
+
+    A step is one fused kernel (`adm_sched_step_ex` with `unipc_table`, csrc/k_unipc.hip): the row's `adm_sched_coef`, its
+    `adm_unipc_coef` and three per-element state buffers (the corrected sample of the previous row, two data predictions). Built:
+    `solver_order` 1 and 2, `solver_type` bh1 / bh2, `predict_x0=True`, the three prediction types, `thresholding`, `lower_order_final`,
+    `disable_corrector`, the three timestep spacings, `final_sigmas_type` zero / sigma_min, `rescale_betas_zero_snr`. Everything else
+    raises NotImplementedError naming the key. Keys of another scheduler's config are dropped."""
+    _class_name = "UniPCMultistepScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                     sample_max_value=1.0, predict_x0=True, solver_type="bh2", lower_order_final=True, disable_corrector=(),
+                     solver_p=None, use_karras_sigmas=False, timestep_spacing="linspace", steps_offset=0, final_sigmas_type="zero",
+                     rescale_betas_zero_snr=False)
+
+    def __init__(self, **kwargs):
+        known = {k: v for k, v in kwargs.items() if k in self._defaults}
+        if "disable_corrector" in known:
+            known["disable_corrector"] = [int(i) for i in (known["disable_corrector"] or ())]
+        else:
+            known["disable_corrector"] = []
+        super().__init__(**known)
+        self._unknown = {k: v for k, v in kwargs.items() if k not in self._defaults and not k.startswith("_")}
+        self._reset_run()
+
+    def _check_config(self, cfg):
+        super()._check_config(cfg)
+
+        def only(key, allowed):
+            if cfg[key] not in allowed:
+                raise NotImplementedError(f"{key}={cfg[key]!r} is not implemented (implemented: {', '.join(map(repr, allowed))})")
+        only("solver_order", (1, 2))
+        only("solver_type", ("bh1", "bh2"))
+        only("predict_x0", (True,))
+        only("solver_p", (None,))
+        only("final_sigmas_type", ("zero", "sigma_min"))
+        if cfg["use_karras_sigmas"]:
+            raise NotImplementedError(f"use_karras_sigmas={cfg['use_karras_sigmas']!r} is not implemented")
+
+    def _reset_run(self):
+        self._hist = None          # (2,B,C,H,W): the data predictions of the two previous eager steps (rewritten in place by the kernel)
+        self._last = None          # (B,C,H,W): the corrected sample of the previous eager step
+        self._last_index = None    # row of the previous eager step; the next row continues the run, any other starts a new one
+        self._run_start = 0
+        self._run_tables = {}      # (device, first row of the run) -> (coef table, unipc table) on the device
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        N = int(num_inference_steps)
+        ts = _solver_timesteps(self.config, N)
+        self._refuse_epsilon_at_zero_snr(ts)
+        self.num_inference_steps = N
+        self.timesteps = torch.from_numpy(ts)
+        self._table = None
+        self._reset_run()
+
+    # ---- coefficient rows -------------------------------------------------------------------------------
+    def _levels(self):
+        """float64 (alpha_i, sigma_i, lambda_i) for i = 0..N; level N is the end of the run (sigma 0, or the sigma of timestep 0). A
+        timestep with alphas_cumprod == 0 (zero terminal SNR) is (0, 1, -inf)."""
+        acp = self.alphas_cumprod.double().numpy()
+        out = []
+        for t in self.timesteps.tolist() + ([] if self.config.final_sigmas_type == "zero" else [0]):
+            if acp[t] == 0.0:
+                out.append((0.0, 1.0, -math.inf))
+                continue
+            sg = math.sqrt((1 - acp[t]) / acp[t])
+            a = 1.0 / math.sqrt(sg * sg + 1.0)
+            s_ = sg * a
+            out.append((a, s_, math.log(a) - math.log(s_)))
+        if self.config.final_sigmas_type == "zero":
+            out.append((1.0, 0.0, math.inf))
+        return out
+
+    def _run_rows(self, run_start):
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps first")
+        self._refuse_epsilon_at_zero_snr(self.timesteps)
+        cfg = self.config
+        rows = unipc_rows(self._levels(), cfg.solver_order, cfg.solver_type, run_start, cfg.lower_order_final, cfg.disable_corrector)
+        for r, t in zip(rows, self.timesteps.tolist()):
+            r["timestep"] = float(t)
+        return rows
+
+    def loop_rows(self, start_step=0, stop_step=None):
+        """Rows [start_step:stop_step] of a run that starts at `start_step` (no corrector and first order there): what the native loop
+        is given."""
+        return self._run_rows(start_step)[start_step:stop_step]
+
+    def coef_rows(self, eta=0.0):
+        """The whole schedule from its first row. `eta` is accepted for the callers that pass it to every scheduler and is ignored: the
+        solver is deterministic (no row has a noise term)."""
+        return self._run_rows(0)
+
+    # ---- eager step ---------------------------------------------------------------------------------------
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, *,
+             model_output_uncond=None, guidance_scale=None, guidance_rescale=None):
+        """One fused kernel. The scheduler holds the state (`last`, the two-slot history); the first call after `set_timesteps`, and any
+        call that does not continue the previous one (another row than the next, another shape or device), starts a new run: no
+        corrector and a first-order predictor there."""
+        i = self._index_of(timestep)
+        fresh = (self._last is None or self._last.shape != sample.shape or self._last.device != sample.device)
+        if fresh or self._last_index is None or i != self._last_index + 1:
+            self._run_start = i
+        if fresh:
+            self._last = torch.empty(sample.shape, dtype=torch.float32, device=sample.device)
+            self._hist = torch.empty((2,) + tuple(sample.shape), dtype=torch.float32, device=sample.device)
+        key = (str(sample.device), self._run_start)
+        if key not in self._run_tables:
+            rows = self._run_rows(self._run_start)
+            self._run_tables = {key: (ops.sched_coef_table(rows, sample.device), ops.sched_unipc_table(rows, sample.device))}
+        table, utable = self._run_tables[key]
+        prev = ops.sched_unipc(sample.contiguous(), model_output.contiguous(), table, utable, self._hist, self._last, i,
+                               uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
+                               guidance_scale=guidance_scale, guidance_rescale=guidance_rescale, threshold=self.threshold(),
+                               prediction=self.prediction)
         self._last_index = i
         if not return_dict:
             return (prev,)

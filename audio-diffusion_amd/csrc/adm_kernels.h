@@ -22,11 +22,17 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
   // from the device block nblock (the captured loop: the handle's, rewritten before every run) or, when it is null, from nvals
   int philox = 0; const uint32_t* nblock = nullptr; uint32_t nvals[4] = {0, 0, 0, 0};
   long per_sample = 0, n4 = 0, mask_bstride = 0;          // derived from the shape by launch_sched_step
+  // k_unipc.hip (the UniPC predictor-corrector step; include/adm.h "UniPC"): one adm_unipc_coef per row of `table`, the corrected sample
+  // of the previous row (B,C,H,W), and `hist` is then the two-slot history (2,B,C,H,W)
+  const adm_unipc_coef* unipc_table = nullptr; float* last = nullptr;
 };
 int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, hipStream_t st);
 int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
 int launch_step_advance(int* step_dev, hipStream_t st);
 int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred = PRED_EPSILON, const char* who = "sched_threshold");   // the selection alone: p.scale[b] = s_b
+int launch_guidance_stats(const SchedStepParams& p, hipStream_t st, const char* who);   // the rescale factors alone: p.rescale[b] = r_b (nothing when p.guidance_rescale == 0)
+// k_unipc.hip: statistics (guidance_rescale != 0) -> selection (mode SCHED_THRESH) -> unipc_step_kernel, on the one stream
+int launch_unipc_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
 int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

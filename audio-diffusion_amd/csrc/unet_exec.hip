@@ -45,6 +45,10 @@ struct adm_unet {
   int coef_cap = 0;
   float* khist_dev = nullptr;    // per-step history coefficient of the multistep loop, beside coef_dev
   int khist_cap = 0;
+  float* unipc_buf = nullptr;    // the UniPC loop's state: the two history slots, then `last` (three times eps_buf's size); allocated with
+                                 // the plan by the first UniPC loop at this batch size, as eps_uncond_buf is
+  adm_unipc_coef* unipc_dev = nullptr;   // per-step adm_unipc_coef of the UniPC loop, beside coef_dev
+  int unipc_cap = 0;
   int* step_dev = nullptr;
   // the noise-stream block of adm_sample_loop_philox: {seed_lo, seed_hi, row_offset, stream id}. Allocated once and never moved (its address
   // is in the captured graph's key); rewritten from noise_blk_host by a stream-ordered copy before every run.
@@ -265,6 +269,7 @@ static void free_plan(adm_unet* h) {
   h->extra.clear();
   h->planned_B = 0;
   h->eps_uncond_buf = nullptr;
+  h->unipc_buf = nullptr;
   h->warm_B = 0;       // the next capture is preceded by an uncaptured forward again (another kernel's one-time set-up)
 #if !defined(ADM_EMU)
   if (h->gexec) {                     // (a replay may still be in flight: drain the stream it ran on before the executable graph goes)
@@ -345,6 +350,14 @@ static int ensure_khist(adm_unet* h, const float* k_hist_host, int n, hipStream_
   return copy_h2d(h->khist_dev, k_hist_host, sizeof(float) * (size_t)n, st);
 }
 
+static int ensure_unipc(adm_unet* h, const adm_unipc_coef* unipc_host, int n, hipStream_t st) {
+  if (h->unipc_cap < n) {
+    ADM_TRY(dalloc(h, (void**)&h->unipc_dev, sizeof(adm_unipc_coef) * (size_t)n));
+    h->unipc_cap = n;
+  }
+  return copy_h2d(h->unipc_dev, unipc_host, sizeof(adm_unipc_coef) * (size_t)n, st);
+}
+
 // adm_sample_loop_args::mode inside this file: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
 // (adm_encode_loop only; adm_sample_loop_ex refuses it)
 enum { LOOP_ENCODE = -1 };
@@ -390,7 +403,12 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
       p.guidance_rescale = a.guidance_rescale; p.rescale = h->rescale_buf;   // (0: off, the buffer is not touched)
     }
     if (a.noise_source == 1) { p.philox = 1; p.nblock = h->noise_blk_dev; }
-    ADM_TRY(launch_sched_step(p, a.mode, st, a.prediction));
+    if (a.unipc_host != nullptr) {   // the UniPC step: two history slots, then last, in the handle's one buffer
+      p.unipc_table = h->unipc_dev; p.hist = h->unipc_buf; p.last = h->unipc_buf + 2 * n;
+      ADM_TRY(launch_unipc_step(p, a.mode, st, a.prediction));
+    } else {
+      ADM_TRY(launch_sched_step(p, a.mode, st, a.prediction));
+    }
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
   return 0;
@@ -405,10 +423,14 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
   if (a.encoding_uncond != nullptr && h->eps_uncond_buf == nullptr)
     ADM_TRY(extra_alloc(h, (void**)&h->eps_uncond_buf,
                         sizeof(float) * (size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
+  if (a.unipc_host != nullptr && h->unipc_buf == nullptr)
+    ADM_TRY(extra_alloc(h, (void**)&h->unipc_buf,
+                        sizeof(float) * 3 * (size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
 #if defined(ADM_EMU)
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
+  if (a.unipc_host != nullptr) ADM_TRY(ensure_unipc(h, a.unipc_host, a.n_steps, st));
   if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, st));
   for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
   return 0;
@@ -424,6 +446,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
   }
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, run));
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
+  if (a.unipc_host != nullptr) ADM_TRY(ensure_unipc(h, a.unipc_host, a.n_steps, run));
   if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, run));
   if (!use_graph) {
     for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
@@ -433,6 +456,8 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
                                  (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
                                  (uint64_t)h->net.ctx_S, (uint64_t)a.prediction};   // (pred: the kernel itself is baked into the captured node)
     if (a.mode == SCHED_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
+    // the UniPC step: another kernel in the captured node, reading the handle's state buffer and table
+    if (a.unipc_host != nullptr) { key.push_back(0x400000000ull); key.push_back((uint64_t)h->unipc_buf); key.push_back((uint64_t)h->unipc_dev); }
     if (a.mode == SCHED_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
       uint32_t wb, mb;
       memcpy(&wb, &a.w, 4); memcpy(&mb, &a.max_value, 4);
@@ -739,6 +764,13 @@ int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* strea
   ADM_REQUIRE(a->guidance_rescale == 0.f || a->encoding_uncond != nullptr,
               "sample_loop: guidance_rescale needs encoding_uncond (it rescales the guided output)");
   ADM_REQUIRE(a->prediction >= PRED_EPSILON && a->prediction <= PRED_V, "sample_loop: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  if (a->unipc_host != nullptr) {
+    ADM_REQUIRE(a->mode != SCHED_MULTISTEP, "sample_loop: with unipc_host, mode must be 0 (x0 as predicted) or 1 (thresholded); 2 (the multistep step) is another step");
+    ADM_REQUIRE(a->step_noise == nullptr, "sample_loop: step_noise must be NULL with unipc_host (the UniPC step has no noise rows)");
+    ADM_REQUIRE(a->noise_source == 0, "sample_loop: noise_source must be 0 with unipc_host (the UniPC step has no noise rows)");
+    ADM_REQUIRE(a->unipc_host[0].c_t == 0.f && a->unipc_host[0].p_m1 == 0.f,
+                "sample_loop: the first row of a UniPC run has no corrector and a first-order predictor (unipc_host[0].c_t == 0 and p_m1 == 0)");
+  }
   if (a->mode == SCHED_MULTISTEP) {
     ADM_REQUIRE(a->k_hist_host != nullptr, "sample_loop: the multistep loop needs k_hist_host");
     ADM_REQUIRE(a->prediction == PRED_EPSILON, "sample_loop: the multistep loop is epsilon only and not thresholded");

@@ -271,6 +271,11 @@ typedef struct adm_sched_step_args {
   int row_offset;            /* noise_source 1: >= 0 and row_offset + B within 32 bits */
   float guidance_rescale;    /* adm_version() >= 115. 0: off; otherwise phi in (0, 1], and needs eps_uncond and rescale ("guidance rescale" below) */
   float* rescale;            /* (B,) device, caller-owned: receives r_b, as scale receives s_b */
+  const struct adm_unipc_coef* unipc_table;   /* adm_version() >= 116 ("UniPC" below). NULL: the steps above. Otherwise the UniPC step: one
+                                row per row of coef_table; `hist` is then the TWO-slot history (2,B,C,H,W) and k_hist_table is ignored;
+                                mode 0 (x0 as predicted) or 1 (thresholded, needs scale), mode 2 is refused; noise must be NULL and
+                                noise_source 0 (each refused by name) */
+  float* last;               /* the UniPC step: (B,C,H,W) device, the corrected sample of the previous row; read where c_t != 0, always written */
 } adm_sched_step_args;
 int adm_sched_step_ex(const adm_sched_step_args* a, void* stream);
 /* The selection alone (adm_sched_threshold and its _pred / _guided forms): reads x, eps, eps_uncond, guidance_scale, coef_table, step_dev,
@@ -296,6 +301,42 @@ int adm_sched_threshold_ex(const adm_sched_step_args* a, void* stream);
  * guidance_rescale == 0 is the path of version 114, bit for bit, and the statistics kernel is not launched. Refused: a guidance_rescale
  * outside [0, 1] or not finite; guidance_rescale != 0 with eps_uncond == NULL (encoding_uncond == NULL for the loop); guidance_rescale != 0
  * with rescale == NULL (adm_sched_step_ex, adm_sched_threshold_ex; the loop's buffer is the handle's). */
+
+/* UniPC (adm_version() >= 116): Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion
+ * Models"; config names follow diffusers' `UniPCMultistepScheduler` [3P-recall: restated from memory, diffusers is not consulted, so the
+ * arithmetic is unpinned like the multistep solver's; tests/test_unipc.py anchors it independently]. THE definition; the kernel
+ * (csrc/k_unipc.hip), the scheduler (schedulers.py `unipc_rows`) and the documents refer to it. Data-prediction form, orders 1 and 2.
+ *
+ * Levels i = 0..N, float64 (alpha_i, sigma_i, lambda_i = ln alpha_i - ln sigma_i): level i < N is the i-th timestep of the schedule, level N
+ * is sigma = 0 (lambda = +inf) or the sigma of timestep 0. A zero-SNR first level has alpha = 0, lambda = -inf.
+ * Data prediction m_i: the x0 prediction at row i from the sample x the model was evaluated on: x0 of the row's prediction type (the
+ *   table under adm_sched_step_pred) of o, o the guided / rescaled output under guidance; thresholded (mode 1): clamp(x0, -s_b, s_b) / s_b with
+ *   s_b of adm_sched_threshold. There is no static clip (coef_table's clip is -1 and is not read).
+ * B(h), for h > 0 with hh = -h, phi = expm1(hh):  solver_type bh2: B = phi;  bh1: B = hh.
+ * Corrector vector b(h, K): g = phi/hh - 1, f = 1; for k = 1..K: b_k = g*f/B, f <- f*(k+1), g <- g/hh - 1/f.
+ * Orders, for a run that starts at row r: predictor order p_i = min(solver_order, i - r + 1, N - i if lower_order_final); row i > r has a
+ *   corrector unless i - 1 is in disable_corrector, of order q_i = p_(i-1). A level with lambda = -inf is never used as history: the order
+ *   that would need it is lowered by one.
+ * Corrector (re-does the move i-1 -> i now that m_i is known), h = lambda_i - lambda_(i-1), r1 = (lambda_(i-2) - lambda_(i-1)) / h:
+ *   q = 1: rho = [0.5];  q = 2: rho solves [[1, 1], [r1, 1]] rho = b(h, 2)
+ *   x_c = (sigma_i/sigma_(i-1)) x_last - alpha_i phi m_(i-1) - alpha_i B ( [q = 2] rho_1 (m_(i-2) - m_(i-1)) / r1 + rho_last (m_i - m_(i-1)) )
+ *   x_last: the corrected sample of row i-1 (the model input itself on row r). Without a corrector x_c = x.
+ *   h = +inf (level i-1 at zero SNR): phi = B = -1 and q = 1.
+ * Predictor (moves i -> i+1 from x_c), h = lambda_(i+1) - lambda_i, r1' = (lambda_(i-1) - lambda_i) / h:
+ *   x' = (sigma_(i+1)/sigma_i) x_c - alpha_(i+1) phi m_i - [p = 2] alpha_(i+1) B 0.5 (m_(i-1) - m_i) / r1'
+ *   lambda_(i+1) = +inf: x' = m_i, written out (the k_x*x_c product is not formed);  lambda_i = -inf: phi = B = -1, x' = sigma_(i+1) x_c + alpha_(i+1) m_i.
+ * Both stages are linear in (x_last, m_(i-1), m_(i-2), m_i, x_c), so a row is the adm_sched_coef of coef_table — sqrt_alpha, sqrt_beta of
+ * level i, k_x = sigma_(i+1)/sigma_i, k_x0 = the coefficient of m_i in x', clip = -1, k_eps = k_noise = 0, timestep — and one adm_unipc_coef:
+ *   x_c = c_x*x_last + c_t*m_i + c_m1*m_(i-1) + c_m2*m_(i-2)       applied iff c_t != 0 (otherwise x_c = x and x_last is not read)
+ *   x'  = k_x0*m_i + k_x*x_c + p_m1*m_(i-1)                         k_x*x_c formed iff k_x != 0
+ * all computed in float64 on the host and rounded to fp32 once. m_(i-1) is read only where c_m1 != 0 || p_m1 != 0, m_(i-2) only where
+ * c_m2 != 0: the first row of a run (c_t = c_m1 = c_m2 = p_m1 = 0) finds last and both history slots uninitialised.
+ * State: last (B,C,H,W) receives x_c on every row; hist (2,B,C,H,W): row s (the index into the tables) reads m_(i-2) from slot s & 1 and
+ * then writes m_i there, and reads m_(i-1) from slot (s - 1) & 1. The mask overwrite goes on `out` only. out may alias x.
+ * Traffic of a full row: 20 B/elem read + 12 B/elem written, +4 read under guidance. */
+typedef struct adm_unipc_coef {
+  float c_x, c_m1, c_m2, c_t, p_m1;
+} adm_unipc_coef;
 
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
@@ -620,6 +661,10 @@ typedef struct adm_sample_loop_args {
   uint64_t seed;
   int row_offset;
   float guidance_rescale;    /* adm_version() >= 115: "guidance rescale" above; 0: off; otherwise needs encoding_uncond */
+  const adm_unipc_coef* unipc_host;   /* adm_version() >= 116: NULL, or n_steps host rows: the UniPC loop ("UniPC" above; mode 0 or 1, any
+                                prediction, step_noise NULL and noise_source 0). Row 0 must have c_t == 0 && p_m1 == 0 (a run starts
+                                without state). The handle owns `last` and the two history slots; their address joins the captured
+                                graph's key as the multistep history's does */
 } adm_sample_loop_args;
 int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
