@@ -72,13 +72,17 @@ class AudioDiffusion:
                                        step_generator: torch.Generator = None, eta: float = 0, noise: torch.Tensor = None,
                                        encoding: torch.Tensor = None, guidance_scale: float = None,
                                        negative_encoding: torch.Tensor = None, device_noise_seed: int = None,
-                                       guidance_rescale: float = 0.0) -> Tuple[Image.Image, Tuple[int, np.ndarray]]:
+                                       guidance_rescale: float = 0.0, frames: int = None, window_stride: int = None,
+                                       circular: bool = False) -> Tuple[Image.Image, Tuple[int, np.ndarray]]:
         """Unconditional (or `encoding`-conditioned) sample from noise (`__init__.py:35-68`). `guidance_scale` > 1 and
         `negative_encoding`: classifier-free guidance, `guidance_rescale`: its rescaled form (Lin et al. 2023 §3.4), `device_noise_seed`:
-        all noise drawn on the device from its own counter-based stream, all as `AudioDiffusionPipeline.__call__` documents them."""
+        all noise drawn on the device from its own counter-based stream, `frames`, `window_stride` and `circular`: a spectrogram wider
+        than the model (and seamless on a circle) sampled through overlapping windows, all as `AudioDiffusionPipeline.__call__` documents
+        them."""
         return self._one(steps=steps, generator=generator, step_generator=step_generator, eta=eta, noise=noise,
                          encoding=encoding, guidance_scale=guidance_scale, negative_encoding=negative_encoding,
-                         device_noise_seed=device_noise_seed, guidance_rescale=guidance_rescale)
+                         device_noise_seed=device_noise_seed, guidance_rescale=guidance_rescale, frames=frames,
+                         window_stride=window_stride, circular=circular)
 
     def generate_spectrogram_and_audio_from_audio(self, audio_file: str = None, raw_audio: np.ndarray = None, slice: int = 0,
                                                   start_step: int = 0, steps: int = None, generator: torch.Generator = None,

@@ -64,6 +64,7 @@ class SampleLoopArgs(C.Structure):     # include/adm.h: adm_sample_loop_args
         ("use_graph", C.c_int), ("mode", C.c_int), ("prediction", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float),
         ("max_value", C.c_float), ("encoding_uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise_source", C.c_int),
         ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float), ("unipc_host", C.POINTER(SchedUnipcCoef)),
+        ("window_total_w", C.c_int), ("window_stride", C.c_int), ("window_wrap", C.c_int),   # "Windowed sampling"; window_total_w 0: off
     ]
 
 
@@ -133,6 +134,8 @@ _SIGS = {
                               [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint64, C.c_int]),
     "adm_sched_step_ex": (C.c_int, [C.POINTER(SchedStepArgs), C.c_void_p]),
     "adm_sched_threshold_ex": (C.c_int, [C.POINTER(SchedStepArgs), C.c_void_p]),
+    "adm_window_gather": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
+    "adm_window_blend": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
     "adm_noise_and_velocity": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_long, C.c_void_p]),
     "adm_add_noise": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                 C.c_int, C.c_int, C.c_long, C.c_void_p]),

@@ -8,6 +8,9 @@ heavy parts are batched on the device:
 * `outpaint`       — cell 16: extend a clip segment by segment; every new segment is generated with its first
                      `overlap_secs` pinned to the tail of the previous one (`mask_start_secs`): the per-step mask overwrite
                      is part of the captured denoising graph (csrc/k_sched.hip `sched_step_kernel`, every instantiation), not a Python loop.
+* `generate_long`  — not in the notebook: a clip longer than the model, or a seamless loop, sampled JOINTLY through overlapping
+                     windows in one batched pipeline call (`frames` / `window_stride` / `circular`), where `outpaint` is causal and
+                     runs the whole pipeline once per segment.
 * `remix_track`    — cell 20: re-generate a whole track in overlapping slices from `start_step`, re-inserting (peak-
                      normalised) the tail of what was generated into the head of the next slice.
 
@@ -63,6 +66,35 @@ def outpaint(pipe, raw_audio: np.ndarray, n_segments: int, overlap_secs: float, 
         track = np.concatenate([track, audio2[ov:]])
         audio = audio2
     return track, images
+
+
+def long_placement(pipe, seconds: float, overlap_secs: float, circular: bool = False) -> Tuple[int, int]:
+    """`seconds` of audio and `overlap_secs` of overlap between neighbouring windows, as the (frames, window_stride) of windowed sampling
+    (include/adm.h "Windowed sampling") for this pipeline's model width W and Mel settings; one column is hop_length / sample_rate
+    seconds. Rounded to the placement rules: the stride W - overlap to the nearest multiple of 4 in [4, W]; the number of windows up, so
+    that the clip is at least `seconds` long (frames = W + k*stride open, k*stride >= W circular)."""
+    cols_per_sec = pipe.mel.get_sample_rate() / pipe.mel.hop_length
+    W = pipe.unet._hw()[1]
+    stride = int(round((W - overlap_secs * cols_per_sec) / 4)) * 4
+    stride = min(max(stride, 4), W)
+    want = max(int(np.ceil(seconds * cols_per_sec)), W)
+    if circular:
+        return -(-want // stride) * stride, stride
+    return W + -(-(want - W) // stride) * stride, stride
+
+
+@torch.no_grad()
+def generate_long(pipe, seconds: float, overlap_secs: float, circular: bool = False, **call):
+    """A clip of about `seconds`, longer than the model was trained on, sampled jointly through model-sized windows that overlap by about
+    `overlap_secs` — ONE batched pipeline call (`frames`, `window_stride`, `circular` of `AudioDiffusionPipeline.__call__`) where
+    `outpaint` runs the whole pipeline once per segment. `circular=True`: the spectrogram tiles with no seam (the Griffin-Lim phase
+    does not). Returns (result of the pipeline call, dict(frames, window_stride, seconds, overlap_secs)): the values as rounded to the
+    placement rules (`long_placement`), in columns and back in seconds. `call`: further keywords of the pipeline call."""
+    frames, stride = long_placement(pipe, seconds, overlap_secs, circular)
+    secs_per_col = pipe.mel.hop_length / pipe.mel.get_sample_rate()
+    used = dict(frames=frames, window_stride=stride, seconds=frames * secs_per_col,
+                overlap_secs=(pipe.unet._hw()[1] - stride) * secs_per_col)
+    return pipe(frames=frames, window_stride=stride, circular=circular, **call), used
 
 
 @torch.no_grad()

@@ -82,6 +82,53 @@ def randn(shape, seed, row_offset=0, t=0, noise_stream=0, device=None):
     return out
 
 
+def window_count(total_w, W, stride, wrap=False, names=("total_w", "stride", "wrap")):
+    """The placement rules of windowed sampling (include/adm.h "Windowed sampling") -> nW, the number of windows per wide sample.
+    A broken rule is a ValueError that names the argument it is about, by the caller's name for it (`names`: total_w, stride, wrap)."""
+    n_total, n_stride, n_wrap = names
+    if not isinstance(wrap, (bool, np.bool_)) and wrap not in (0, 1):
+        raise ValueError(f"{n_wrap}={wrap!r} must be a bool")
+    total_w, W, stride = int(total_w), int(W), int(stride)
+    if W <= 0 or W % 4:
+        raise ValueError(f"the model's width {W} must be a positive multiple of 4 for windowed sampling ({n_total})")
+    if stride <= 0 or stride % 4 or stride > W:
+        raise ValueError(f"{n_stride}={stride} must be a positive multiple of 4 and at most the model's width {W}")
+    if total_w % 4 or total_w < W:
+        raise ValueError(f"{n_total}={total_w} must be a multiple of 4 and at least the model's width {W}")
+    if wrap:
+        if total_w % stride:
+            raise ValueError(f"{n_total}={total_w} must be a multiple of {n_stride}={stride} with {n_wrap}=True")
+        return total_w // stride
+    if (total_w - W) % stride:
+        raise ValueError(f"{n_total}={total_w} minus the model's width {W} must be a multiple of {n_stride}={stride} with {n_wrap}=False")
+    return (total_w - W) // stride + 1
+
+
+def window_gather(x, W, stride, wrap=False):
+    """x (B, C, H, Wt) -> the windows (B*nW, C, H, W), sample-major: windows[b*nW + w, c, y, j] = x[b, c, y, col(w, j)] with
+    col = w*stride + j, modulo Wt when `wrap` (include/adm.h "Windowed sampling"; csrc/k_window.hip). A copy, bit-exact."""
+    _f32(x)
+    B, Cc, H, Wt = x.shape
+    nW = window_count(Wt, W, stride, wrap)
+    out = torch.empty((B * nW, Cc, H, int(W)), dtype=torch.float32, device=x.device)
+    N.check(N.lib().adm_window_gather(N.ptr(x), N.ptr(out), B, Cc, H, Wt, int(W), int(stride), int(bool(wrap)), N.stream_for(x)))
+    return out
+
+
+def window_blend(windows, total_w, stride, wrap=False):
+    """windows (B*nW, C, H, W), as `window_gather` lays them out -> (B, C, H, total_w): per column the mean of the windows that cover it,
+    summed in ascending window index from the first window's value, one division by the cover count (include/adm.h "Windowed sampling")."""
+    _f32(windows)
+    BW, Cc, H, W = windows.shape
+    nW = window_count(total_w, W, stride, wrap)
+    if BW % nW:
+        raise ValueError(f"{BW} windows are not a multiple of the {nW} windows per sample of total_w={total_w}, stride={stride}, wrap={wrap}")
+    out = torch.empty((BW // nW, Cc, H, int(total_w)), dtype=torch.float32, device=windows.device)
+    N.check(N.lib().adm_window_blend(N.ptr(windows), N.ptr(out), BW // nW, Cc, H, int(total_w), W, int(stride), int(bool(wrap)),
+                                     N.stream_for(windows)))
+    return out
+
+
 def _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out=None, u8_out=None, noise=None, mask=None,
                 mask_start=0, mask_end=0, guidance_rescale=None, rescale_out=None):
     """The `adm_sched_step_args` (include/adm.h) of a plain step on x, eps: (B,C,H,W); the callers add their mode's fields.

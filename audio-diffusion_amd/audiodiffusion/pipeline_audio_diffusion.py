@@ -200,9 +200,41 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             if given is not None:
                 raise ValueError(f"device_noise_seed draws the noise on the device from its own stream: it cannot be combined with `{name}`")
 
+    def _window(self, frames, window_stride, circular, **excluded):
+        """The rules of windowed sampling (`__call__`), before any work. -> None (`frames` is None: today's path), or
+        (frames, window_stride, circular, windows per sample)."""
+        if frames is None:
+            if window_stride is not None:
+                raise ValueError("window_stride places the windows of a wide sample: it needs `frames`")
+            if circular:
+                raise ValueError("circular places the windows of a wide sample on a circle: it needs `frames`")
+            return None
+        for name, given in excluded.items():
+            if given:
+                raise ValueError(f"`{name}` cannot be combined with `frames`: windowed sampling starts from noise and has no mask "
+                                 f"(the mask's layout assumes the model's width)")
+        if self.vqvae is not None:
+            raise NotImplementedError("`frames` with a `vqvae` is not implemented: the decoder's mid-block attention would see another "
+                                      "sequence length than the one it was trained on")
+        W = self.unet._hw()[1]
+        stride = W // 2 if window_stride is None else window_stride
+        nW = ops.window_count(frames, W, stride, circular, names=("frames", "window_stride", "circular"))
+        return int(frames), int(stride), bool(circular), nW
+
+    def _wide_mel(self, frames):
+        """A Mel of the pipeline's Mel config with x_res = frames (the codec requires the image width to equal x_res): a separate object,
+        kept for the next call at the same width; the pipeline's own Mel is not touched."""
+        cfg = dict(self.mel.config, x_res=int(frames))
+        kept = getattr(self, "_wide_mel_kept", None)
+        if kept is None or kept[0] != cfg:
+            kept = (cfg, Mel.from_config(cfg))
+            self._wide_mel_kept = kept
+        kept[1].nnls_max_iter = self.mel.nnls_max_iter
+        return kept[1]
+
     def _denoise(self, images, start_step, eta, step_generator, mask, mask_start, mask_end, step_noise=None,
                  use_graph=True, want_u8=True, encoding=None, stop_step=None, guidance_scale=None, negative_encoding=None,
-                 device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=0.0):
+                 device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=0.0, window_stride=None, circular=False):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
         before that step index, so that a single step of a long schedule can be compared in isolation.
         Every combination is one `adm_sample_loop_args` (include/adm.h) and one `adm_sample_loop_ex` call per chunk.
@@ -211,7 +243,11 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         per step, and the step uses the rescaled guided output (include/adm.h "guidance rescale").
         device_noise_seed: the noise of every noisy row is drawn inside the step kernel ("adm noise stream 1", include/adm.h) at (seed,
         device_noise_row_offset + b, the row's timestep): ONE native call whatever the number of steps, no staging tensor, no chunks,
-        no synchronisation. A schedule without noisy rows (DDIM with eta == 0, the multistep solver) has nothing to draw."""
+        no synchronisation. A schedule without noisy rows (DDIM with eta == 0, the multistep solver) has nothing to draw.
+        window_stride (not None: windowed sampling, include/adm.h "Windowed sampling"): `images` is the WIDE sample (B, C, H, frames),
+        wider than the model, which keeps its own width; every step gathers the windows, runs the model on all B*nW of them as one
+        batch, blends the outputs and steps once on the wide sample, inside the same native call. `circular` places the windows on a
+        circle. The encodings of sample b serve its nW windows."""
         sched, unet = self.scheduler, self.unet
         self._device_noise(device_noise_seed, step_generator=step_generator, step_noise=step_noise)
         guided = self._guided(guidance_scale, negative_encoding, encoding)
@@ -225,11 +261,22 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         n = len(rows)
         x = images.contiguous().clone()  # the reference never writes the loop state back into `noise`
         B, Cc, H, W = x.shape
-        if tuple(unet._hw()) != (H, W):
+        nW = 1
+        if window_stride is not None:   # the model keeps its own width: x is wide, the windows have the model's shape
+            if mask is not None:
+                raise ValueError("windowed sampling has no mask (the mask's layout assumes the model's width)")
+            if unet._hw()[0] != H:
+                raise ValueError(f"a wide sample has the model's height {unet._hw()[0]}, not {H}")
+            nW = ops.window_count(W, unet._hw()[1], window_stride, circular, names=("frames", "window_stride", "circular"))
+        elif tuple(unet._hw()) != (H, W):
             unet.sample_size = (H, W)
         h = unet._ensure_handle()
         if isinstance(unet, UNet2DConditionModel):     # `self.unet(images, t, encoding)` (:160-161): constant over the loop
-            unet._set_encoding(h, encoding, B, x.device)
+            if nW > 1 and encoding is not None:        # sample-major windows: the encoding of sample b for each of its nW windows
+                encoding = encoding.repeat_interleave(nW, dim=0)
+                if negative_encoding is not None and negative_encoding.shape[0] == B:
+                    negative_encoding = negative_encoding.repeat_interleave(nW, dim=0)
+            unet._set_encoding(h, encoding, B * nW, x.device)
         if guided:
             # kept alive, and reused by the next call: the captured graph holds the pointer
             unet._enc_uncond, unet._enc_uncond_buf = self._negative_encoding(negative_encoding, unet._enc,
@@ -285,6 +332,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             if philox:   # noise drawn in the step kernel: no staging tensor
                 args.noise_source, args.row_offset = 1, int(device_noise_row_offset)
                 args.seed = ops._seed64(device_noise_seed, "device_noise_seed")
+            if window_stride is not None:   # x, the noise and the u8 image are `W` wide; B counts wide samples
+                args.window_total_w, args.window_stride, args.window_wrap = W, int(window_stride), int(bool(circular))
             N.check(N.lib().adm_sample_loop_ex(h, args, N.stream_for(x)))
             if x.is_cuda and (noise_ptr is not None or mask_ptr is not None) and not last:
                 torch.cuda.current_stream(x.device).synchronize()  # staging buffers are rewritten next chunk
@@ -317,6 +366,9 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         device_noise_seed: int = None,
         device_noise_row_offset: int = 0,
         guidance_rescale: float = 0.0,
+        frames: int = None,
+        window_stride: int = None,
+        circular: bool = False,
     ) -> Union[PipelineOutput, Tuple[List[Image.Image], Tuple[int, List[np.ndarray]]]]:
         """Generate random mel spectrogram from audio input and convert to audio (reference docstring `:89-112`).
 
@@ -345,24 +397,41 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         eta > 0) draws inside the fused step kernel, and the loop is one native call without a noise tensor. Sample b is global row
         `device_noise_row_offset` + b, so a sample's bits depend on neither its batch nor its shard. It is NOT torch.randn's stream: the
         same seed gives other images than a torch generator. With `generator`, `step_generator` or `step_noise` it is a ValueError; with
-        the multistep and UniPC schedulers (no noisy steps) the seed only picks the initial latent."""
+        the multistep and UniPC schedulers (no noisy steps) the seed only picks the initial latent.
+
+        Windowed sampling, off by default: `frames`, `window_stride`, `circular` (include/adm.h "Windowed sampling"). `frames` = Wt asks
+        for spectrograms Wt columns wide, wider than the model's W: every step cuts the wide sample into model-sized windows `window_stride`
+        (default W // 2) apart, runs the model on the windows of all samples as one batch, averages the model outputs where windows
+        overlap and makes one scheduler step on the wide sample, all inside the captured loop. `circular=True` places the windows on a
+        circle: the time axis has no edge and the spectrogram tiles with no seam at any column.
+          * `frames=None` is the path without it, exactly. frames, window_stride and W are multiples of 4, window_stride <= W <= frames;
+            open: frames - W is a multiple of window_stride; circular: frames is. Otherwise ValueError naming the keyword.
+          * `noise`, if given, is (batch_size, C, H, frames); device noise draws the initial latent at that shape. Everything per sample
+            (thresholding, guidance rescale, the device-noise counter) is per wide sample. `encoding` rows serve all windows of a sample.
+          * `window_stride` or `circular` without `frames`, and `audio_file`, `raw_audio`, `mask_start_secs` or `mask_end_secs` with it:
+            ValueError. With a `vqvae`: NotImplementedError.
+          * images come back `frames` wide; audio is decoded through a separate Mel of this pipeline's Mel config with x_res = frames
+            and is hop_length * (frames - 1) samples long. The Griffin-Lim phase of a circular image is NOT made circular: the seamless
+            object is the spectrogram."""
         ops.guidance_rescale_on(guidance_rescale, self._guided(guidance_scale, negative_encoding, encoding))   # the ValueErrors, before any work
         self._device_noise(device_noise_seed, generator=generator, step_generator=step_generator, step_noise=step_noise)
-        steps = steps or self.get_default_steps()
-        self.scheduler.set_timesteps(steps)
-        step_generator = step_generator or generator
         # For backwards compatibility
         if type(self.unet.sample_size) == int:
             self.unet.sample_size = (self.unet.sample_size, self.unet.sample_size)
+        window = self._window(frames, window_stride, circular, audio_file=audio_file, raw_audio=raw_audio is not None,
+                              mask_start_secs=mask_start_secs, mask_end_secs=mask_end_secs)
+        steps = steps or self.get_default_steps()
+        self.scheduler.set_timesteps(steps)
+        step_generator = step_generator or generator
+        shape = (batch_size, self.unet.in_channels, self.unet.sample_size[0], self.unet.sample_size[1] if window is None else window[0])
+        if window is not None and noise is not None and tuple(noise.shape) != shape:
+            raise ValueError(f"noise shape {tuple(noise.shape)} is not (batch_size, C, H, frames) = {shape}")
         if noise is None and device_noise_seed is not None:
-            noise = ops.randn((batch_size, self.unet.in_channels, self.unet.sample_size[0], self.unet.sample_size[1]), device_noise_seed,
-                              row_offset=device_noise_row_offset, t=0, noise_stream=1, device=self.device)
+            noise = ops.randn(shape, device_noise_seed, row_offset=device_noise_row_offset, t=0, noise_stream=1, device=self.device)
         if noise is None:
             # the reference's torch.randn(..., generator=generator, device=self.device) (:120-128); going through
             # randn_tensor additionally accepts a CPU generator on the GPU build (drawn on the host, then moved)
-            noise = randn_tensor(
-                (batch_size, self.unet.in_channels, self.unet.sample_size[0], self.unet.sample_size[1]),
-                generator, self.device, torch.float32)
+            noise = randn_tensor(shape, generator, self.device, torch.float32)
         images = noise
         mask = None
         mask_start = mask_end = 0
@@ -397,7 +466,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                                    step_noise=step_noise, want_u8=self.vqvae is None, encoding=encoding,
                                    guidance_scale=guidance_scale, negative_encoding=negative_encoding,
                                    device_noise_seed=device_noise_seed, device_noise_row_offset=device_noise_row_offset,
-                                   guidance_rescale=guidance_rescale)
+                                   guidance_rescale=guidance_rescale, window_stride=None if window is None else window[1],
+                                   circular=window is not None and window[2])
 
         if self.vqvae is not None:
             # 0.18215 was scaling factor used in training to ensure unit variance (pipeline:187-190); the 1/0.18215
@@ -417,7 +487,10 @@ class AudioDiffusionPipeline(DiffusionPipeline):
 
         # the reference maps image_to_audio over the images one by one on a host core (:201); here the whole batch goes
         # through the Mel kernels in one launch sequence
-        audios = list(self.mel.images_to_audios(images, init_phase=init_phase)) if audio else []
+        audios = []
+        if audio:
+            mel = self.mel if window is None else self._wide_mel(window[0])   # (the codec requires the image width to equal x_res)
+            audios = list(mel.images_to_audios(images, init_phase=init_phase))
         if return_float:
             return images, final_float
         if not return_dict:

@@ -43,6 +43,12 @@ int launch_slerp_grid(const float* x0, const float* x1, long n, const double* al
                       double* scratch3, hipStream_t st);
 int launch_dequant(const float* x, uint8_t* out, long n, hipStream_t st);
 
+// k_window.hip (include/adm.h "Windowed sampling"): the placement rules, each refused by `who` and the name of its argument (`pre` +
+// total_w / stride / wrap) -> *nW windows per wide sample; the gather and the blend
+int window_count(const char* who, const char* pre, int total_w, int W, int stride, int wrap, int* nW);
+int launch_window_gather(const float* x, float* windows, int B, int C, int H, int total_w, int W, int stride, int wrap, hipStream_t st);
+int launch_window_blend(const float* windows, float* out, int B, int C, int H, int total_w, int W, int stride, int wrap, hipStream_t st);
+
 // k_groupnorm.hip
 int launch_groupnorm_finalize(const double* st1, int C1, int tiles1, const double* st2, int C2, int tiles2, int N, int HW,
                               int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift,

@@ -49,6 +49,10 @@ struct adm_unet {
                                  // the plan by the first UniPC loop at this batch size, as eps_uncond_buf is
   adm_unipc_coef* unipc_dev = nullptr;   // per-step adm_unipc_coef of the UniPC loop, beside coef_dev
   int unipc_cap = 0;
+  // the windowed loop (include/adm.h "Windowed sampling"): the gathered windows (the forwards' input) and the blended model outputs of
+  // the wide shape (the step's eps / eps_uncond). Each of eps_buf's size — nW*W >= Wt, so a wide tensor fits where the windows do —
+  // allocated with the plan by the first windowed loop at this batch size, as eps_uncond_buf is
+  float *win_buf = nullptr, *wide_eps_buf = nullptr, *wide_uncond_buf = nullptr;
   int* step_dev = nullptr;
   // the noise-stream block of adm_sample_loop_philox: {seed_lo, seed_hi, row_offset, stream id}. Allocated once and never moved (its address
   // is in the captured graph's key); rewritten from noise_blk_host by a stream-ordered copy before every run.
@@ -270,6 +274,7 @@ static void free_plan(adm_unet* h) {
   h->planned_B = 0;
   h->eps_uncond_buf = nullptr;
   h->unipc_buf = nullptr;
+  h->win_buf = h->wide_eps_buf = h->wide_uncond_buf = nullptr;
   h->warm_B = 0;       // the next capture is preceded by an uncaptured forward again (another kernel's one-time set-up)
 #if !defined(ADM_EMU)
   if (h->gexec) {                     // (a replay may still be in flight: drain the stream it ran on before the executable graph goes)
@@ -374,32 +379,64 @@ static int ensure_noise_block(adm_unet* h, const LoopArgs& a, hipStream_t st) {
   return copy_h2d(h->noise_blk_dev, h->noise_blk_host, sizeof(h->noise_blk_host), st);
 }
 
+// The windowed loop (LoopArgs::window_total_w != 0; include/adm.h "Windowed sampling"): windows per wide sample. adm_sample_loop_ex has
+// checked the placement, so the count is the definition's quotient.
+static int loop_windows(const adm_unet* h, const LoopArgs& a) {
+  if (a.window_total_w == 0) return 1;
+  return a.window_wrap ? a.window_total_w / a.window_stride : (a.window_total_w - h->cfg.sample_w) / a.window_stride + 1;
+}
+
+static int gather_windows(adm_unet* h, const LoopArgs& a, hipStream_t st) {
+  const adm_unet_config& c = h->cfg;
+  return launch_window_gather(a.x, h->win_buf, a.B, c.in_channels, c.sample_h, a.window_total_w, c.sample_w, a.window_stride,
+                              a.window_wrap, st);
+}
+
 // One denoising step; every step-dependent scalar is read on the device through *step_dev.
 static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st) {
   const adm_unet_config& c = h->cfg;
   const adm_sched_coef* table = h->coef_dev;
-  ADM_TRY(run_forward(h, a.x, h->eps_buf, a.B, table, st));
+  // windowed: gather, the forward(s) on the windows as ONE batch of B*nW, one blend per model output, then the step on the wide tensors
+  const bool windowed = a.window_total_w != 0;
+  const int FB = a.B * loop_windows(h, a);                      // the forwards' batch
+  const int Wx = windowed ? a.window_total_w : c.sample_w;      // the width of x, and of everything the step touches
+  const float* fx = a.x;
+  if (windowed) {
+    ADM_TRY(gather_windows(h, a, st));
+    fx = h->win_buf;
+  }
+  ADM_TRY(run_forward(h, fx, h->eps_buf, FB, table, st));
   if (a.encoding_uncond != nullptr) {
     // The unconditional branch: a second forward of batch B on the SAME plan (its side-stream hoists included), with the encoding pointer
     // swapped. Nothing derived from the encoding outlives a forward (the cross-attention kernel projects K and V from net.ctx inside every
     // launch), so the swap is all it takes; both forwards run in stream order, the second after the first has joined its side launches.
     const float* ctx_cond = h->net.ctx;
     h->net.ctx = a.encoding_uncond;
-    const int rc = run_forward(h, a.x, h->eps_uncond_buf, a.B, table, st);
+    const int rc = run_forward(h, fx, h->eps_uncond_buf, FB, table, st);
     h->net.ctx = ctx_cond;
     ADM_TRY(rc);
   }
-  const long n = (long)a.B * c.in_channels * c.sample_h * c.sample_w;
+  const float *eps = h->eps_buf, *eps_uncond = h->eps_uncond_buf;
+  if (windowed) {
+    ADM_TRY(launch_window_blend(eps, h->wide_eps_buf, a.B, c.out_channels, c.sample_h, Wx, c.sample_w, a.window_stride, a.window_wrap, st));
+    eps = h->wide_eps_buf;
+    if (a.encoding_uncond != nullptr) {
+      ADM_TRY(launch_window_blend(eps_uncond, h->wide_uncond_buf, a.B, c.out_channels, c.sample_h, Wx, c.sample_w, a.window_stride,
+                                  a.window_wrap, st));
+      eps_uncond = h->wide_uncond_buf;
+    }
+  }
+  const long n = (long)a.B * c.in_channels * c.sample_h * Wx;
   if (a.mode == LOOP_ENCODE) {
-    ADM_TRY(launch_encode_step(a.x, h->eps_buf, table, h->step_dev, step, n, st));
+    ADM_TRY(launch_encode_step(a.x, eps, table, h->step_dev, step, n, st));
   } else {
-    SchedStepParams p{a.x, h->eps_buf, a.step_noise, a.x, a.u8_out, table, h->step_dev, step, a.mask, a.n_steps, a.mask_start,
-                      a.mask_end, a.B, c.in_channels, c.sample_h, c.sample_w};
+    SchedStepParams p{a.x, eps, a.step_noise, a.x, a.u8_out, table, h->step_dev, step, a.mask, a.n_steps, a.mask_start,
+                      a.mask_end, a.B, c.in_channels, c.sample_h, Wx};
     p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
     p.lo = a.lo; p.hi = a.hi; p.w = a.w; p.max_value = a.max_value; p.scale = h->scale_buf;
     p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
     if (a.encoding_uncond != nullptr) {
-      p.eps_uncond = h->eps_uncond_buf; p.guidance = a.guidance_scale;
+      p.eps_uncond = eps_uncond; p.guidance = a.guidance_scale;
       p.guidance_rescale = a.guidance_rescale; p.rescale = h->rescale_buf;   // (0: off, the buffer is not touched)
     }
     if (a.noise_source == 1) { p.philox = 1; p.nblock = h->noise_blk_dev; }
@@ -419,13 +456,24 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
   const int use_graph = a.use_graph;
   ADM_TRY(finalize(h));
   ADM_REQUIRE(h->cfg.in_channels == h->cfg.out_channels, "sample_loop: in/out channels differ");
-  ADM_TRY(plan(h, a.B));
+  // the plan's batch: the forwards' (B*nW windows with window_total_w != 0). Every per-plan buffer below is sized by it, and the wide
+  // sample's state (history, UniPC state, per-sample factors) lives in the same buffers: nW*W >= Wt and PB >= B
+  const int PB = a.B * loop_windows(h, a);
+  const size_t plan_elems = (size_t)PB * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w;
+  if (a.window_total_w != 0)
+    ADM_REQUIRE((size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * a.window_total_w <= plan_elems,
+                "sample_loop: the wide sample does not fit the buffers of the windows' plan (window_total_w > nW * sample_w)");
+  ADM_TRY(plan(h, PB));
   if (a.encoding_uncond != nullptr && h->eps_uncond_buf == nullptr)
-    ADM_TRY(extra_alloc(h, (void**)&h->eps_uncond_buf,
-                        sizeof(float) * (size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
+    ADM_TRY(extra_alloc(h, (void**)&h->eps_uncond_buf, sizeof(float) * plan_elems));
   if (a.unipc_host != nullptr && h->unipc_buf == nullptr)
-    ADM_TRY(extra_alloc(h, (void**)&h->unipc_buf,
-                        sizeof(float) * 3 * (size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w));
+    ADM_TRY(extra_alloc(h, (void**)&h->unipc_buf, sizeof(float) * 3 * plan_elems));
+  if (a.window_total_w != 0) {
+    if (h->win_buf == nullptr) ADM_TRY(extra_alloc(h, (void**)&h->win_buf, sizeof(float) * plan_elems));
+    if (h->wide_eps_buf == nullptr) ADM_TRY(extra_alloc(h, (void**)&h->wide_eps_buf, sizeof(float) * plan_elems));
+    if (a.encoding_uncond != nullptr && h->wide_uncond_buf == nullptr)
+      ADM_TRY(extra_alloc(h, (void**)&h->wide_uncond_buf, sizeof(float) * plan_elems));
+  }
 #if defined(ADM_EMU)
   (void)use_graph;
   ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
@@ -476,6 +524,12 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
     }
     // the noise stream: the block's address (the handle's, stable) and nothing else; the seed and the row offset are data behind it
     if (a.noise_source == 1) { key.push_back(0x200000000ull); key.push_back((uint64_t)h->noise_blk_dev); }
+    // the windowed step: two or three more captured nodes, the placement baked into their arguments, and the handle's three buffers
+    if (a.window_total_w != 0) {
+      key.push_back(0x500000000ull); key.push_back((uint64_t)a.window_total_w); key.push_back((uint64_t)a.window_stride);
+      key.push_back((uint64_t)a.window_wrap); key.push_back((uint64_t)h->win_buf); key.push_back((uint64_t)h->wide_eps_buf);
+      key.push_back((uint64_t)h->wide_uncond_buf);
+    }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
         // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
@@ -487,12 +541,14 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
         (void)hipGraphExecDestroy(h->gexec);
         h->gexec = nullptr;
       }
-      if (h->warm_B != a.B) {
+      if (h->warm_B != PB) {
         // One UNCAPTURED forward (into eps_buf; the sample is not touched) before the first capture at this batch size:
         // the launchers' one-time work — constant buffers (hipMalloc + null-stream copy), hipFuncSetAttribute for the
         // >64 KiB LDS kernels, device-attribute queries — is not legal inside a stream capture.
-        ADM_TRY(run_forward(h, a.x, h->eps_buf, a.B, h->coef_dev, run));
-        h->warm_B = a.B;
+        // Windowed: a.x holds B wide samples, fewer elements than the PB windows the forward reads: it reads the gathered windows.
+        if (a.window_total_w != 0) ADM_TRY(gather_windows(h, a, run));
+        ADM_TRY(run_forward(h, a.window_total_w != 0 ? h->win_buf : a.x, h->eps_buf, PB, h->coef_dev, run));
+        h->warm_B = PB;
       }
       hipGraph_t graph = nullptr;
       ADM_HIP_OK(hipStreamBeginCapture(run, hipStreamCaptureModeThreadLocal));
@@ -785,6 +841,13 @@ int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* strea
     ADM_REQUIRE(((long)h->cfg.in_channels * h->cfg.sample_h * h->cfg.sample_w) % 4 == 0, "sample_loop: C*H*W must be a multiple of 4");
     for (int i = 0; i < a->n_steps; ++i)   // the counter's third word is the row's timestep as an integer
       ADM_REQUIRE(a->coef_host[i].timestep >= 0.f && a->coef_host[i].timestep < 2147483648.f, "sample_loop: every timestep must be in [0, 2^31)");
+  }
+  if (a->window_total_w != 0) {   // windowed (include/adm.h "Windowed sampling"); 0: off, and window_stride / window_wrap are ignored
+    ADM_REQUIRE(a->B > 0, "sample_loop: bad argument");
+    ADM_REQUIRE(a->mask == nullptr, "sample_loop: mask must be NULL with window_total_w (the mask's layout assumes the model's width)");
+    int nW = 0;
+    ADM_TRY(window_count("sample_loop", "window_", a->window_total_w, h->cfg.sample_w, a->window_stride, a->window_wrap, &nW));
+    ADM_REQUIRE((long)a->B * nW <= 2147483647L, "sample_loop: B times the number of windows (window_total_w, window_stride) must fit in an int");
   }
   return run_loop_fp32(h, *a, stream);
 }

@@ -338,6 +338,33 @@ typedef struct adm_unipc_coef {
   float c_x, c_m1, c_m2, c_t, p_m1;
 } adm_unipc_coef;
 
+/* Windowed sampling (adm_version() >= 117): one wide sample denoised jointly through overlapping model-sized windows, the model outputs
+ * averaged where windows overlap and ONE scheduler step made on the wide sample (the fusion of Bar-Tal et al. 2023, "MultiDiffusion",
+ * applied to the model output before the step). THE definition; the kernels (csrc/k_window.hip), the loop (csrc/unet_exec.hip) and the
+ * documents refer to it.
+ * Shapes: the model's sample is (C,H,W); the wide sample is (C,H,Wt) (Wt = total_w; the Python API's `frames`); stride s.
+ *   Required: W % 4 == 0, s % 4 == 0, Wt % 4 == 0 and 0 < s <= W <= Wt.
+ * Placement:
+ *   open     (wrap = 0)  requires (Wt - W) % s == 0;  nW = (Wt - W)/s + 1 windows;  window w covers columns [w*s, w*s + W)
+ *   circular (wrap = 1)  requires Wt % s == 0;        nW = Wt/s windows;            window w covers columns (w*s + j) mod Wt, j in [0, W)
+ *   With W <= Wt no window covers a column twice. On the circle the time axis has no edge: the seam is a column like any other.
+ * Gather:  windows[(b*nW + w), c, y, j] = x[b, c, y, col(w, j)].  A copy, bit-exact. Rows are sample-major: the nW windows of sample b
+ *   are contiguous.
+ * Blend:   mean[b, c, y, col] = (o_w0 + o_w1 + ...) / float(count)  over the windows that cover col, in ASCENDING window index; the sum
+ *   starts from the first window's value (not from zero), every addition is rounded to fp32 on its own, and there is one IEEE division
+ *   by the integer cover count converted to float. A column covered once gives o itself. No atomics: the result depends on neither the
+ *   launch geometry nor a replay.
+ * Step:    one scheduler step of the existing kind on the wide tensors, (x, mean) -> x' at shape (B,C,H,Wt). Everything that is per
+ *   sample is per WIDE sample: the thresholding statistic is over n = C*H*Wt; the guidance-rescale factor is per wide sample; the
+ *   device-noise counter is (float4 index inside the wide sample, row_offset + b, timestep); the multistep and UniPC state has the wide
+ *   shape. Under guidance both forwards run on the same gathered windows and both outputs are blended before u + g*(c - u).
+ * Where the step is not affine in the model output (the clip clamp, thresholding) "average the model outputs, then step once" IS the
+ * definition; it is not the same as "step each window, then average".
+ * Both entry points refuse, by the name of the argument (total_w, stride or wrap), every placement rule above; null pointers, B <= 0 and
+ * a B*nW past int are refused too. Traffic: gather 8 B per window element; blend 4 B read per window element + 4 B written per wide one. */
+int adm_window_gather(const float* x, float* windows, int B, int C, int H, int total_w, int W, int stride, int wrap, void* stream);
+int adm_window_blend(const float* windows, float* out, int B, int C, int H, int total_w, int W, int stride, int wrap, void* stream);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -665,6 +692,14 @@ typedef struct adm_sample_loop_args {
                                 prediction, step_noise NULL and noise_source 0). Row 0 must have c_t == 0 && p_m1 == 0 (a run starts
                                 without state). The handle owns `last` and the two history slots; their address joins the captured
                                 graph's key as the multistep history's does */
+  int window_total_w, window_stride, window_wrap;   /* adm_version() >= 117: "Windowed sampling" above. window_total_w == 0: off, and the
+                                other two are ignored. Otherwise x and u8_out are (B,C,sample_h,window_total_w), step_noise is
+                                (n_steps,B,C,sample_h,window_total_w), B counts WIDE samples, the handle is planned at batch B*nW (its
+                                encodings have B*nW rows, sample-major) and one captured step is: gather into a handle-owned window
+                                buffer, the forward(s) at batch B*nW, one blend per forward output into handle-owned wide buffers, the
+                                step at W = window_total_w, the counter's increment. The three fields and those buffers' addresses are
+                                part of the captured graph's key: one handle may alternate windowed and ordinary loops. Refused by
+                                name: mask != NULL, and every placement rule (window_total_w, window_stride, window_wrap) */
 } adm_sample_loop_args;
 int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
