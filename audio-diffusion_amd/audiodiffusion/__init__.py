@@ -88,13 +88,17 @@ class AudioDiffusion:
                                                   start_step: int = 0, steps: int = None, generator: torch.Generator = None,
                                                   mask_start_secs: float = 0, mask_end_secs: float = 0,
                                                   step_generator: torch.Generator = None, eta: float = 0,
-                                                  encoding: torch.Tensor = None, noise: torch.Tensor = None
+                                                  encoding: torch.Tensor = None, noise: torch.Tensor = None, keep_mask=None,
+                                                  known_level: str = "previous", frames: int = None
                                                   ) -> Tuple[Image.Image, Tuple[int, np.ndarray]]:
         """Variation / in- and out-painting of one slice of an audio input (`__init__.py:70-122`): `start_step` keeps the
-        input noised to that step, `mask_*_secs` pin the start / end of the spectrogram to the input."""
+        input noised to that step, `mask_*_secs` pin the start / end of the spectrogram to the input. `keep_mask`, `known_level`,
+        `frames` (not in the reference): region in-painting under an arbitrary (H, W) keep mask, optionally `frames` wide
+        (`AudioDiffusionPipeline.__call__`)."""
         return self._one(audio_file=audio_file, raw_audio=raw_audio, slice=slice, start_step=start_step, steps=steps,
                          generator=generator, mask_start_secs=mask_start_secs, mask_end_secs=mask_end_secs,
-                         step_generator=step_generator, eta=eta, noise=noise, encoding=encoding)
+                         step_generator=step_generator, eta=eta, noise=noise, encoding=encoding, keep_mask=keep_mask,
+                         known_level=known_level, frames=frames)
 
     @staticmethod
     def loop_it(audio: np.ndarray, sample_rate: int, loops: int = 12) -> np.ndarray:

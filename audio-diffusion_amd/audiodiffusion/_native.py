@@ -54,6 +54,8 @@ class SchedStepArgs(C.Structure):      # include/adm.h: adm_sched_step_args
         ("lo", C.c_int), ("hi", C.c_int), ("w", C.c_float), ("max_value", C.c_float), ("scale", C.c_void_p), ("noise_source", C.c_int),
         ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float), ("rescale", C.c_void_p),
         ("unipc_table", C.c_void_p), ("last", C.c_void_p),
+        ("known", C.c_void_p), ("known_noise", C.c_void_p), ("keep", C.c_void_p), ("known_table", C.c_void_p),   # "Region in-painting"; keep NULL: off
+        ("known_batched", C.c_int), ("keep_batched", C.c_int),
     ]
 
 
@@ -65,6 +67,8 @@ class SampleLoopArgs(C.Structure):     # include/adm.h: adm_sample_loop_args
         ("max_value", C.c_float), ("encoding_uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise_source", C.c_int),
         ("seed", C.c_uint64), ("row_offset", C.c_int), ("guidance_rescale", C.c_float), ("unipc_host", C.POINTER(SchedUnipcCoef)),
         ("window_total_w", C.c_int), ("window_stride", C.c_int), ("window_wrap", C.c_int),   # "Windowed sampling"; window_total_w 0: off
+        ("known", C.c_void_p), ("known_noise", C.c_void_p), ("keep", C.c_void_p), ("known_coef_host", c_float_p),   # "Region in-painting"; keep NULL: off
+        ("known_batched", C.c_int), ("keep_batched", C.c_int),
     ]
 
 

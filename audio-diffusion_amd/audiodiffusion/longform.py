@@ -11,6 +11,10 @@ heavy parts are batched on the device:
 * `generate_long`  — not in the notebook: a clip longer than the model, or a seamless loop, sampled JOINTLY through overlapping
                      windows in one batched pipeline call (`frames` / `window_stride` / `circular`), where `outpaint` is causal and
                      runs the whole pipeline once per segment.
+* `inpaint`        — not in the notebook: regenerate given time spans of a clip and keep the rest of its spectrogram exactly
+                     (`keep_mask`: the known region is re-noised inside the step kernel, include/adm.h "Region in-painting").
+* `continue_track` — not in the notebook: the one-call counterpart of `outpaint`: ONE windowed call over a wide sample whose
+                     first columns are pinned to the input.
 * `remix_track`    — cell 20: re-generate a whole track in overlapping slices from `start_step`, re-inserting (peak-
                      normalised) the tail of what was generated into the head of the next slice.
 
@@ -95,6 +99,45 @@ def generate_long(pipe, seconds: float, overlap_secs: float, circular: bool = Fa
     used = dict(frames=frames, window_stride=stride, seconds=frames * secs_per_col,
                 overlap_secs=(pipe.unet._hw()[1] - stride) * secs_per_col)
     return pipe(frames=frames, window_stride=stride, circular=circular, **call), used
+
+
+def span_keep_mask(pipe, spans_secs: Sequence[Tuple[float, float]], width: int = None) -> np.ndarray:
+    """The (H, W) uint8 keep mask that regenerates the time spans `spans_secs` [(from, to), ...] and keeps everything else: seconds
+    become columns by the pipeline's own rule for `mask_start_secs` (pixels_per_second = W * sample_rate / x_res / hop_length,
+    truncated), each span covering columns [int(from * pps), int(to * pps)). `width`: the mask's width (default: the model's W)."""
+    H, W = pipe.unet._hw()
+    pps = W * pipe.mel.get_sample_rate() / pipe.mel.x_res / pipe.mel.hop_length
+    keep = np.ones((H, W if width is None else int(width)), dtype=np.uint8)
+    for a, b in spans_secs:
+        if not 0 <= a <= b:
+            raise ValueError(f"spans_secs: a span is (from, to) with 0 <= from <= to, not {(a, b)}")
+        keep[:, int(a * pps):int(b * pps)] = 0
+    return keep
+
+
+@torch.no_grad()
+def inpaint(pipe, raw_audio: np.ndarray, spans_secs: Sequence[Tuple[float, float]], **call):
+    """Regenerate the time spans `spans_secs` [(from, to), ...] of one slice of `raw_audio` and keep the rest of its spectrogram
+    exactly (`keep_mask` of `AudioDiffusionPipeline.__call__` with the default `known_level="previous"`): ONE pipeline call, the
+    known region re-noised inside the step kernel. Returns (result of the pipeline call, the (H, W) keep mask). `call`: further
+    keywords of the pipeline call (`slice`, `steps`, `batch_size`, `noise`, ...)."""
+    keep = span_keep_mask(pipe, spans_secs)
+    return pipe(raw_audio=raw_audio, keep_mask=keep, **call), keep
+
+
+@torch.no_grad()
+def continue_track(pipe, raw_audio: np.ndarray, seconds: float, overlap_secs: float, **call):
+    """Continue `raw_audio` to a clip of about `seconds` in ONE windowed pipeline call: the wide sample of `long_placement(pipe,
+    seconds, overlap_secs)` is denoised jointly through overlapping windows, the columns the input covers (hop_length samples each, from
+    column 0) are kept and the rest is generated. The one-call counterpart of `outpaint`, which runs the whole pipeline once per
+    segment at batch 1. Returns (result of the pipeline call, dict(frames, window_stride, kept_columns, seconds)). `call`: further
+    keywords of the pipeline call."""
+    frames, stride = long_placement(pipe, seconds, overlap_secs)
+    kept = min(frames, int(len(raw_audio) / pipe.mel.hop_length))
+    keep = np.zeros((pipe.unet._hw()[0], frames), dtype=np.uint8)
+    keep[:, :kept] = 1
+    used = dict(frames=frames, window_stride=stride, kept_columns=kept, seconds=frames * pipe.mel.hop_length / pipe.mel.get_sample_rate())
+    return pipe(raw_audio=raw_audio, keep_mask=keep, frames=frames, window_stride=stride, **call), used
 
 
 @torch.no_grad()

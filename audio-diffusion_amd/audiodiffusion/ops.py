@@ -149,6 +149,28 @@ def _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance
     return a, keep
 
 
+def _set_known(a, known):
+    """The known-region fields of `a` (include/adm.h "Region in-painting"). known: None, or (known, known_noise, keep, known_table):
+    known (1 or B, C, H, W) fp32, known_noise (B, C, H, W) fp32, keep (1 or B, H, W) uint8, known_table (n, 2) fp32 of (ka, kb) per row of
+    the coefficient table. -> the tensors the struct points to (they must outlive the native call)."""
+    if known is None:
+        return None
+    kn, kz, keep, table = known
+    _f32(kn), _f32(kz), _f32(table)
+    shape = (a.B, a.C, a.H, a.W)
+    if keep.dtype != torch.uint8 or not keep.is_contiguous() or tuple(keep.shape[1:]) != shape[2:] or keep.shape[0] not in (1, a.B):
+        raise ValueError(f"keep must be a contiguous uint8 tensor (1 or B, H, W) = (1 or {a.B}, {a.H}, {a.W}), not {keep.dtype} {tuple(keep.shape)}")
+    if tuple(kn.shape[1:]) != shape[1:] or kn.shape[0] not in (1, a.B):
+        raise ValueError(f"known must be (1 or B, C, H, W) = (1 or {a.B}, {a.C}, {a.H}, {a.W}), not {tuple(kn.shape)}")
+    if tuple(kz.shape) != shape:
+        raise ValueError(f"known_noise must be (B, C, H, W) = {shape}, not {tuple(kz.shape)}")
+    if table.dim() != 2 or table.shape[1] != 2:
+        raise ValueError(f"known_table must be (n, 2), not {tuple(table.shape)}")
+    a.known, a.known_noise, a.keep, a.known_table = N.ptr(kn), N.ptr(kz), N.ptr(keep), N.ptr(table)
+    a.known_batched, a.keep_batched = int(kn.shape[0] == a.B and a.B > 1), int(keep.shape[0] == a.B and a.B > 1)
+    return known
+
+
 def _set_threshold(a, ratio, max_value, scale):
     """The selection's fields of `a`: the ranks of `ratio` over one sample, the maximum and the (B,) tensor that receives the thresholds."""
     a.lo, a.hi, a.w = threshold_ranks(a.C * a.H * a.W, ratio)
@@ -173,7 +195,7 @@ def sched_threshold(x, eps, coef_table, step, ratio, max_value, step_dev=None, o
 
 def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None, u8_out=None, threshold=None,
                step_dev=None, scale_out=None, prediction=0, uncond=None, guidance_scale=None, noise_seed=None, noise_row_offset=0,
-               guidance_rescale=None, rescale_out=None):
+               guidance_rescale=None, rescale_out=None, known=None):
     """Fused scheduler epilogue (pipeline_audio_diffusion.py:165-185,192-194), one native call (`adm_sched_step_ex`). x,eps: (B,C,H,W).
     threshold: None, or (dynamic_thresholding_ratio, sample_max_value): x0 is clamped to its per-sample percentile and divided by it
     instead of the static clamp (scale_out: optional (B,) fp32 that receives the thresholds). step_dev: optional int32 device scalar
@@ -184,7 +206,9 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
     without the tensor; noise_row_offset is the global row of x[0]. guidance_rescale (None or 0: off, the kernels of the unrescaled step):
     phi in (0, 1] rescales the guided output per sample, o' = phi*(o*r_b) + (1 - phi)*o with r_b = std(eps_b) / std(o_b) computed on the
     device first (include/adm.h "guidance rescale"; `guidance_stats_kernel`); needs uncond and guidance_scale. rescale_out: optional (B,)
-    fp32 that receives r_b."""
+    fp32 that receives r_b. known: None, or (known, known_noise, keep, known_table): the known-region overwrite (include/adm.h "Region
+    in-painting"): where keep (1 or B, H, W) uint8 is non-zero the result is ka*known + kb*known_noise with (ka, kb) = known_table[step],
+    `add_noise`'s bits, formed inside the step kernel; excludes `mask`."""
     if noise_seed is not None and noise is not None:
         raise ValueError("`noise_seed` (noise drawn inside the kernel) and `noise=` (a noise tensor) exclude each other")
     out = torch.empty_like(x) if out is None else out
@@ -196,22 +220,25 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
         _set_threshold(a, threshold[0], threshold[1], scale)
     if noise_seed is not None:
         a.noise_source, a.seed, a.row_offset = 1, _seed64(noise_seed, "noise_seed"), int(noise_row_offset)
+    _known = _set_known(a, known)
     N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
     return out
 
 
 def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
-                    u8_out=None, step_dev=None, uncond=None, guidance_scale=None, guidance_rescale=None, rescale_out=None):
+                    u8_out=None, step_dev=None, uncond=None, guidance_scale=None, guidance_rescale=None, rescale_out=None, known=None):
     """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP, ...>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,)
     fp32 beside the (n,8) coef_table. hist is read where k_hist_table[step] != 0 and always rewritten with this step's x0. step_dev:
     optional int32 device scalar that replaces `step`. uncond, guidance_scale: classifier-free guidance as in sched_step; hist then
-    holds x0 of the guided output. guidance_rescale, rescale_out: as in sched_step; hist then holds x0 of the rescaled output."""
+    holds x0 of the guided output. guidance_rescale, rescale_out: as in sched_step; hist then holds x0 of the rescaled output. known: as
+    in sched_step; hist is written before the overwrite and never sees it."""
     _f32(hist), _f32(k_hist_table)
     assert hist.shape == x.shape and k_hist_table.numel() == coef_table.shape[0]
     out = torch.empty_like(x) if out is None else out
     a, _keep = _sched_args(x, eps, coef_table, step, step_dev, 0, uncond, guidance_scale, out, u8_out, noise, mask, mask_start, mask_end,
                            guidance_rescale, rescale_out)
     a.mode, a.k_hist_table, a.hist = N.SCHED_MULTISTEP, N.ptr(k_hist_table), N.ptr(hist)
+    _known = _set_known(a, known)
     N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
     return out
 
@@ -226,14 +253,15 @@ def sched_unipc_table(rows, device):
 
 def sched_unipc(x, eps, coef_table, unipc_table, hist, last, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
                 u8_out=None, step_dev=None, uncond=None, guidance_scale=None, guidance_rescale=None, rescale_out=None, threshold=None,
-                prediction=0, scale_out=None):
+                prediction=0, scale_out=None, known=None):
     """Fused UniPC predictor-corrector step (csrc/k_unipc.hip `unipc_step_kernel`; include/adm.h "UniPC"), one native call
     (`adm_sched_step_ex` with `unipc_table`). x, eps, last: (B,C,H,W); hist: (2,B,C,H,W); unipc_table: (n,5) fp32 beside the (n,8)
     coef_table. Row `step` corrects x with the data predictions of this and the two previous rows (where its c_t != 0; `last` is read only
     then), writes the corrected sample to `last` and this row's data prediction to hist[step & 1], and returns the predicted sample of
     the next level. threshold, prediction, uncond, guidance_scale, guidance_rescale, rescale_out, scale_out, step_dev, mask: as in
     sched_step; the history then holds x0 of the guided / rescaled / thresholded output. `noise` exists for the keyword set of
-    sched_multistep and must be None: the step has no noise rows (the native call refuses it by name)."""
+    sched_multistep and must be None: the step has no noise rows (the native call refuses it by name). known: as in sched_step; `last` and
+    hist are written before the overwrite and never see it."""
     _f32(hist), _f32(last), _f32(unipc_table)
     assert tuple(hist.shape) == (2,) + tuple(x.shape) and last.shape == x.shape and unipc_table.shape == (coef_table.shape[0], 5)
     out = torch.empty_like(x) if out is None else out
@@ -244,6 +272,7 @@ def sched_unipc(x, eps, coef_table, unipc_table, hist, last, step, noise=None, m
         a.mode = N.SCHED_THRESH
         scale = torch.empty((a.B,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
         _set_threshold(a, threshold[0], threshold[1], scale)
+    _known = _set_known(a, known)
     N.check(N.lib().adm_sched_step_ex(a, N.stream_for(x)))
     return out
 

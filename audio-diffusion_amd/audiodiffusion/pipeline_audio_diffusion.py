@@ -221,6 +221,56 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         nW = ops.window_count(frames, W, stride, circular, names=("frames", "window_stride", "circular"))
         return int(frames), int(stride), bool(circular), nW
 
+    KNOWN_LEVELS = ("previous", "current")
+
+    def _keep_mask(self, keep_mask, known_level, known, shape, has_audio, mask_start_secs, mask_end_secs):
+        """The rules of region in-painting (`__call__`), before any work and any native call. `shape`: the (B, C, H, W) of the tensor
+        being denoised. -> None (`keep_mask` is None: today's path), or (keep (1 or B, H, W) uint8 on the device, `known` as a
+        (1 or B, C, H, W) fp32 device tensor or None when the audio input is the source)."""
+        if known_level not in self.KNOWN_LEVELS:
+            raise ValueError(f"known_level={known_level!r} must be one of {self.KNOWN_LEVELS}")
+        if keep_mask is None:
+            if known is not None:
+                raise ValueError("`known` is the image that `keep_mask` keeps: it needs `keep_mask`")
+            return None
+        if mask_start_secs or mask_end_secs:
+            raise ValueError("`keep_mask` cannot be combined with `mask_start_secs` / `mask_end_secs`: put the edge columns into the mask")
+        if known is None and not has_audio:
+            raise ValueError("`keep_mask` needs a source for the region it keeps: `audio_file`, `raw_audio` or `known`")
+        if known is not None and has_audio:
+            raise ValueError("`keep_mask` takes ONE source for the region it keeps: `known`, or `audio_file` / `raw_audio`, not both")
+        B, Cc, H, W = shape
+        keep = torch.as_tensor(np.asarray(keep_mask) if not torch.is_tensor(keep_mask) else keep_mask)
+        if keep.dim() == 2:
+            keep = keep[None]
+        if keep.dim() != 3 or tuple(keep.shape[1:]) != (H, W) or keep.shape[0] not in (1, B):
+            raise ValueError(f"keep_mask shape {tuple(keep.shape)} is not (H, W), (1, H, W) or (B, H, W) with (B, H, W) = {(B, H, W)}: "
+                             f"its resolution is that of the tensor being denoised")
+        # (a contiguous uint8 tensor on the device is used as it is, so its address — part of the captured graph's key — stays the caller's:
+        # new contents in the same buffer replay the graph; the kernel reads "non-zero", not "one")
+        if not (keep.dtype == torch.uint8 and keep.device == torch.device(self.device) and keep.is_contiguous()):
+            keep = (keep != 0).to(torch.uint8).to(self.device).contiguous()
+        if known is not None:
+            if not torch.is_tensor(known) or known.dim() != 4 or tuple(known.shape[1:]) != (Cc, H, W) or known.shape[0] not in (1, B):
+                got = tuple(known.shape) if torch.is_tensor(known) else type(known).__name__
+                raise ValueError(f"known shape {got} is not (1 or B, C, H, W) with (B, C, H, W) = {shape}: a float tensor in model space")
+            known = known.to(self.device, torch.float32).contiguous()
+        return keep, known
+
+    def _known_coef(self, start_step, n, known_level):
+        """(ka, kb) for the `n` loop rows from `start_step`: `add_noise`'s coefficients (`_sa_sb`) of the level the overwrite uses.
+        "current": row i at timesteps[i], the level the sample had before the step (the reference's mask). "previous": row i at
+        timesteps[i + 1], the level it has after the step, and the last row of the schedule (1, 0): the known image itself."""
+        ts = self.scheduler.timesteps
+        first = start_step + (1 if known_level == "previous" else 0)
+        idx = ts[first:start_step + n + (1 if known_level == "previous" else 0)]
+        sa, sb = self.scheduler._sa_sb(idx, "cpu") if len(idx) else (torch.zeros(0), torch.zeros(0))
+        rows = [(float(a), float(b)) for a, b in zip(sa.tolist(), sb.tolist())]
+        if len(rows) < n:   # "previous" on the last row of the schedule
+            rows.append((1.0, 0.0))
+        assert len(rows) == n
+        return rows
+
     def _wide_mel(self, frames):
         """A Mel of the pipeline's Mel config with x_res = frames (the codec requires the image width to equal x_res): a separate object,
         kept for the next call at the same width; the pipeline's own Mel is not touched."""
@@ -234,7 +284,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
 
     def _denoise(self, images, start_step, eta, step_generator, mask, mask_start, mask_end, step_noise=None,
                  use_graph=True, want_u8=True, encoding=None, stop_step=None, guidance_scale=None, negative_encoding=None,
-                 device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=0.0, window_stride=None, circular=False):
+                 device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=0.0, window_stride=None, circular=False,
+                 keep_mask=None, known=None, known_noise=None, known_level="previous"):
         """The denoising loop (`:159-185`) as ONE native call per chunk of steps. `stop_step` (tests only) ends the loop
         before that step index, so that a single step of a long schedule can be compared in isolation.
         Every combination is one `adm_sample_loop_args` (include/adm.h) and one `adm_sample_loop_ex` call per chunk.
@@ -247,7 +298,11 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         window_stride (not None: windowed sampling, include/adm.h "Windowed sampling"): `images` is the WIDE sample (B, C, H, frames),
         wider than the model, which keeps its own width; every step gathers the windows, runs the model on all B*nW of them as one
         batch, blends the outputs and steps once on the wide sample, inside the same native call. `circular` places the windows on a
-        circle. The encodings of sample b serve its nW windows."""
+        circle. The encodings of sample b serve its nW windows.
+        keep_mask (not None: region in-painting, include/adm.h "Region in-painting"): a (H, W), (1, H, W) or (B, H, W) 0/1 mask at the
+        resolution of `images`; after every step the elements it marks are overwritten, inside the step kernel, with
+        ka*known + kb*known_noise at the level `known_level` names (`_known_coef`). known: (1 or B, C, H, W) in model space; known_noise:
+        (B, C, H, W), one fixed draw for all steps. No tensor has a step axis; with windowed sampling the three are wide."""
         sched, unet = self.scheduler, self.unet
         self._device_noise(device_noise_seed, step_generator=step_generator, step_noise=step_noise)
         guided = self._guided(guidance_scale, negative_encoding, encoding)
@@ -284,6 +339,16 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         u8 = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=x.device) if want_u8 else None
         if Cc != 1 and want_u8:
             u8 = None  # NHWC permute for multi-channel images is done after the loop
+        kept = None
+        if keep_mask is not None:
+            if mask is not None:
+                raise ValueError("`keep_mask` and the staged mask exclude each other")
+            if known is None or known_noise is None:
+                raise ValueError("`keep_mask` needs `known` and `known_noise`")
+            checked = self._keep_mask(keep_mask, known_level, known, (B, Cc, H, W), False, 0, 0)
+            kept = (checked[1], known_noise.to(x.device, torch.float32).contiguous(), checked[0], self._known_coef(start_step, n, known_level))
+            if tuple(kept[1].shape) != (B, Cc, H, W):
+                raise ValueError(f"known_noise shape {tuple(kept[1].shape)} is not that of the sample, {(B, Cc, H, W)}")
         needs_noise = [r["k_noise"] != 0.0 for r in rows]
         philox = device_noise_seed is not None and any(needs_noise)
         chunk = n if philox or not any(needs_noise) else min(n, self._STEP_CHUNK)
@@ -334,6 +399,10 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                 args.seed = ops._seed64(device_noise_seed, "device_noise_seed")
             if window_stride is not None:   # x, the noise and the u8 image are `W` wide; B counts wide samples
                 args.window_total_w, args.window_stride, args.window_wrap = W, int(window_stride), int(bool(circular))
+            if kept is not None:   # the known-region overwrite: three tensors of x's shape class and this chunk's (ka, kb) rows
+                args.known, args.known_noise, args.keep = N.ptr(kept[0]), N.ptr(kept[1]), N.ptr(kept[2])
+                args.known_coef_host = (C.c_float * (2 * m))(*[v for row in kept[3][done:done + m] for v in row])
+                args.known_batched, args.keep_batched = int(kept[0].shape[0] != 1), int(kept[2].shape[0] != 1)
             N.check(N.lib().adm_sample_loop_ex(h, args, N.stream_for(x)))
             if x.is_cuda and (noise_ptr is not None or mask_ptr is not None) and not last:
                 torch.cuda.current_stream(x.device).synchronize()  # staging buffers are rewritten next chunk
@@ -369,6 +438,9 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         frames: int = None,
         window_stride: int = None,
         circular: bool = False,
+        keep_mask=None,
+        known_level: str = "previous",
+        known: torch.Tensor = None,
     ) -> Union[PipelineOutput, Tuple[List[Image.Image], Tuple[int, List[np.ndarray]]]]:
         """Generate random mel spectrogram from audio input and convert to audio (reference docstring `:89-112`).
 
@@ -412,18 +484,47 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             ValueError. With a `vqvae`: NotImplementedError.
           * images come back `frames` wide; audio is decoded through a separate Mel of this pipeline's Mel config with x_res = frames
             and is hop_length * (frames - 1) samples long. The Griffin-Lim phase of a circular image is NOT made circular: the seamless
-            object is the spectrogram."""
+            object is the spectrogram.
+
+        Region in-painting, off by default: `keep_mask`, `known_level`, `known` (include/adm.h "Region in-painting"). `keep_mask` is a
+        bool or 0/1 tensor or array (H, W), (1, H, W) or (B, H, W) at the resolution of the tensor being denoised (image pixels; latent
+        cells with a `vqvae`; `frames` wide with windowed sampling); non-zero means "this element stays the input's". Any region: a span
+        in the middle of a clip, a frequency band, single pixels; any channel count (the mask is broadcast over the channels).
+          * `keep_mask=None` is the path without it, exactly.
+          * the known image comes from `audio_file` / `raw_audio` (+ `slice`), converted as for `mask_start_secs` (with a `vqvae`:
+            encoded and scaled by 0.18215; with `frames`: through a Mel of this pipeline's config with x_res = frames), or from `known`,
+            a float tensor (1 or B, C, H, W) already in model space ([-1, 1] images, or scaled latents). One of them is needed, not both.
+          * after every step the kept elements are overwritten with ka*known + kb*noise INSIDE the step kernel: no (B, steps, H, W) mask
+            tensor is built, nothing is staged per step, and the run is the same native call(s) as without the mask.
+          * `known_level="previous"` (default): the overwrite uses the level the sample has AFTER the step (timesteps[i + 1]) and the last
+            step uses (1, 0), so the kept region of the result is the input exactly. `"current"` is the reference's rule (the level of
+            timesteps[i]): with edge columns it gives the images of `mask_start_secs` / `mask_end_secs` byte for byte, the noise of the
+            last timestep included.
+          * the noise is the initial latent, as in the reference: ONE fixed draw for all steps, not a fresh draw per step (copied before
+            `start_step` writes into the latent; with `device_noise_seed` it is the latent that seed draws).
+          * `start_step > 0`: every sample (not only [0, 0] as with `mask_start_secs`) starts from add_noise(known, noise,
+            timesteps[start_step - 1]).
+          * with `mask_start_secs` / `mask_end_secs`, without a source, with a mask or a `known` of another shape, or with another
+            `known_level`: ValueError naming the keyword. `frames` + `vqvae` stays NotImplementedError."""
         ops.guidance_rescale_on(guidance_rescale, self._guided(guidance_scale, negative_encoding, encoding))   # the ValueErrors, before any work
         self._device_noise(device_noise_seed, generator=generator, step_generator=step_generator, step_noise=step_noise)
         # For backwards compatibility
         if type(self.unet.sample_size) == int:
             self.unet.sample_size = (self.unet.sample_size, self.unet.sample_size)
-        window = self._window(frames, window_stride, circular, audio_file=audio_file, raw_audio=raw_audio is not None,
+        has_audio = audio_file is not None or raw_audio is not None
+        if known_level not in self.KNOWN_LEVELS:
+            raise ValueError(f"known_level={known_level!r} must be one of {self.KNOWN_LEVELS}")
+        if keep_mask is not None and (mask_start_secs or mask_end_secs):   # (before `frames` refuses the same two for its own reason)
+            raise ValueError("`keep_mask` cannot be combined with `mask_start_secs` / `mask_end_secs`: put the edge columns into the mask")
+        # (an audio input with `frames` is the known image of a keep mask; without one it stays refused)
+        window = self._window(frames, window_stride, circular, audio_file=audio_file if keep_mask is None else None,
+                              raw_audio=raw_audio is not None and keep_mask is None,
                               mask_start_secs=mask_start_secs, mask_end_secs=mask_end_secs)
         steps = steps or self.get_default_steps()
         self.scheduler.set_timesteps(steps)
         step_generator = step_generator or generator
         shape = (batch_size, self.unet.in_channels, self.unet.sample_size[0], self.unet.sample_size[1] if window is None else window[0])
+        kept = self._keep_mask(keep_mask, known_level, known, shape, has_audio, mask_start_secs, mask_end_secs)
         if window is not None and noise is not None and tuple(noise.shape) != shape:
             raise ValueError(f"noise shape {tuple(noise.shape)} is not (batch_size, C, H, frames) = {shape}")
         if noise is None and device_noise_seed is not None:
@@ -436,7 +537,30 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         mask = None
         mask_start = mask_end = 0
 
-        if audio_file is not None or raw_audio is not None:
+        known_noise = None
+        if kept is not None:
+            # region in-painting: the known image in model space, the latent copied as the ONE noise draw before anything writes into
+            # it, and no (B, steps, H, W) mask: the step kernel forms add_noise(known, noise, level) where keep_mask says so
+            known = kept[1]
+            if known is None:
+                mel = self.mel if window is None else self._wide_mel(window[0])
+                mel.load_audio(audio_file, raw_audio)
+                input_image = mel.audio_slice_to_image(slice)
+                input_image = np.frombuffer(input_image.tobytes(), dtype="uint8").reshape((input_image.height, input_image.width))
+                input_image = (input_image / 255) * 2 - 1
+                input_images = torch.tensor(input_image[np.newaxis, :, :], dtype=torch.float).to(self.device)
+                if self.vqvae is not None:
+                    input_images = self.vqvae.encode(torch.unsqueeze(input_images, 0)).latent_dist.sample(generator=generator)[0]
+                    input_images = 0.18215 * input_images
+                known = input_images[None].contiguous()
+                if tuple(known.shape[1:]) != shape[1:]:
+                    raise ValueError(f"the audio input gives a known image of shape {tuple(known.shape[1:])}, the sample is {shape[1:]}: "
+                                     f"pass `known` at the sample's shape")
+            known_noise = noise.to(self.device, torch.float32).contiguous().clone()
+            if start_step > 0:
+                sa, sb = self.scheduler._sa_sb(self.scheduler.timesteps[start_step - 1].repeat(batch_size), self.device)
+                images = ops.add_noise(known.expand(shape).contiguous(), known_noise, sa, sb, per_sample=True)
+        elif audio_file is not None or raw_audio is not None:
             self.mel.load_audio(audio_file, raw_audio)
             input_image = self.mel.audio_slice_to_image(slice)
             input_image = np.frombuffer(input_image.tobytes(), dtype="uint8").reshape(
@@ -467,7 +591,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                                    guidance_scale=guidance_scale, negative_encoding=negative_encoding,
                                    device_noise_seed=device_noise_seed, device_noise_row_offset=device_noise_row_offset,
                                    guidance_rescale=guidance_rescale, window_stride=None if window is None else window[1],
-                                   circular=window is not None and window[2])
+                                   circular=window is not None and window[2], keep_mask=None if kept is None else kept[0],
+                                   known=known if kept is not None else None, known_noise=known_noise, known_level=known_level)
 
         if self.vqvae is not None:
             # 0.18215 was scaling factor used in training to ensure unit variance (pipeline:187-190); the 1/0.18215

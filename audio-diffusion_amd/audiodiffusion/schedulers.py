@@ -256,8 +256,20 @@ class _SchedulerBase:
             return None
         return float(self.config.dynamic_thresholding_ratio), float(self.config.sample_max_value)
 
+    def _known(self, known, i, device):
+        """`step(known=...)`: None, or (known, known_noise, keep, ka, kb): the known-region overwrite of this one step (include/adm.h
+        "Region in-painting"): where keep (1 or B, H, W) is non-zero the result is ka*known + kb*known_noise. -> the tuple
+        `ops.sched_step(known=...)` takes: the three tensors and a table that holds (ka, kb) on row `i`."""
+        if known is None:
+            return None
+        kn, kz, keep, ka, kb = known
+        table = torch.zeros((i + 1, 2), dtype=torch.float32)
+        table[i, 0], table[i, 1] = float(ka), float(kb)
+        keep = (torch.as_tensor(keep) != 0).to(torch.uint8).to(device).contiguous()
+        return kn.contiguous(), kz.contiguous(), keep[None] if keep.dim() == 2 else keep, table.to(device)
+
     def _step(self, model_output, timestep, sample, eta, generator, variance_noise, model_output_uncond=None, guidance_scale=None,
-              device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=None):
+              device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=None, known=None):
         if device_noise_seed is not None:
             for name, given in (("generator", generator), ("variance_noise", variance_noise)):
                 if given is not None:
@@ -272,7 +284,7 @@ class _SchedulerBase:
                               threshold=self.threshold(), prediction=self.prediction,
                               uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
                               guidance_scale=guidance_scale, noise_seed=device_noise_seed, noise_row_offset=device_noise_row_offset,
-                              guidance_rescale=guidance_rescale)
+                              guidance_rescale=guidance_rescale, known=self._known(known, i, sample.device))
         return SchedulerOutput(prev_sample=prev)
 
 
@@ -308,9 +320,10 @@ class DDPMScheduler(_SchedulerBase):
         return rows
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None, *,
-             model_output_uncond=None, guidance_scale=None, device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=None):
+             model_output_uncond=None, guidance_scale=None, device_noise_seed=None, device_noise_row_offset=0, guidance_rescale=None,
+             known=None):
         return self._step(model_output, timestep, sample, 0.0, generator, variance_noise, model_output_uncond, guidance_scale,
-                          device_noise_seed, device_noise_row_offset, guidance_rescale)
+                          device_noise_seed, device_noise_row_offset, guidance_rescale, known)
 
 
 class DDIMScheduler(_SchedulerBase):
@@ -356,11 +369,11 @@ class DDIMScheduler(_SchedulerBase):
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True, *, model_output_uncond=None, guidance_scale=None, device_noise_seed=None,
-             device_noise_row_offset=0, guidance_rescale=None):
+             device_noise_row_offset=0, guidance_rescale=None, known=None):
         if use_clipped_model_output:
             raise NotImplementedError("use_clipped_model_output is not implemented (the reference never sets it)")
         return self._step(model_output, timestep, sample, float(eta), generator, variance_noise, model_output_uncond, guidance_scale,
-                          device_noise_seed, device_noise_row_offset, guidance_rescale)
+                          device_noise_seed, device_noise_row_offset, guidance_rescale, known)
 
 
 def _f32(v):
@@ -522,7 +535,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
 
     # ---- eager step ---------------------------------------------------------------------------------------
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, *,
-             model_output_uncond=None, guidance_scale=None, guidance_rescale=None):
+             model_output_uncond=None, guidance_scale=None, guidance_rescale=None, known=None):
         """One fused kernel (with model_output_uncond and guidance_scale: the guided one, whose history is x0 of the guided output). First order on the first call after `set_timesteps` (and whenever the call does not continue the
         previous one: another row than the next, another shape or device); the scheduler holds the history tensor."""
         i = self._index_of(timestep)
@@ -539,7 +552,8 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         table, khist = self._ms_tables[key]
         prev = ops.sched_multistep(sample.contiguous(), model_output.contiguous(), table, khist, self._hist, i,
                                    uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
-                                   guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+                                   guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
+                                   known=self._known(known, i, sample.device))
         self._last_index = i
         if not return_dict:
             return (prev,)
@@ -720,7 +734,7 @@ class UniPCMultistepScheduler(_SchedulerBase):
 
     # ---- eager step ---------------------------------------------------------------------------------------
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, *,
-             model_output_uncond=None, guidance_scale=None, guidance_rescale=None):
+             model_output_uncond=None, guidance_scale=None, guidance_rescale=None, known=None):
         """One fused kernel. The scheduler holds the state (`last`, the two-slot history); the first call after `set_timesteps`, and any
         call that does not continue the previous one (another row than the next, another shape or device), starts a new run: no
         corrector and a first-order predictor there."""
@@ -739,7 +753,7 @@ class UniPCMultistepScheduler(_SchedulerBase):
         prev = ops.sched_unipc(sample.contiguous(), model_output.contiguous(), table, utable, self._hist, self._last, i,
                                uncond=model_output_uncond.contiguous() if model_output_uncond is not None else None,
                                guidance_scale=guidance_scale, guidance_rescale=guidance_rescale, threshold=self.threshold(),
-                               prediction=self.prediction)
+                               prediction=self.prediction, known=self._known(known, i, sample.device))
         self._last_index = i
         if not return_dict:
             return (prev,)

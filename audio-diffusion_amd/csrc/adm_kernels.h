@@ -25,6 +25,11 @@ struct SchedStepParams {   // the step kernel's parameter block; the caller fill
   // k_unipc.hip (the UniPC predictor-corrector step; include/adm.h "UniPC"): one adm_unipc_coef per row of `table`, the corrected sample
   // of the previous row (B,C,H,W), and `hist` is then the two-slot history (2,B,C,H,W)
   const adm_unipc_coef* unipc_table = nullptr; float* last = nullptr;
+  // the known-region overwrite (include/adm.h "Region in-painting"; keep == nullptr: off): known (Bk,C,H,W), known_noise (B,C,H,W), keep
+  // (Bm,H,W) bytes, known_table two floats (ka, kb) per row of `table`; the two flags say Bk == B / Bm == B (0: one image, broadcast)
+  const float* known = nullptr; const float* known_noise = nullptr; const uint8_t* keep = nullptr; const float* known_table = nullptr;
+  int known_batched = 0, keep_batched = 0;
+  long plane = 0, known_bstride = 0, keep_bstride = 0;    // derived by sched_known_prepare: H*W and the batch strides in elements
 };
 int launch_randn(float* out, int B, long per_sample, uint64_t seed, int row_offset, int t, int noise_stream, hipStream_t st);
 int launch_sched_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);

@@ -45,11 +45,21 @@
 //           the selection beside it takes 10.3, and 9.2 us against 52.1 at 256 x 256, B = 16). The sums are fp64,
 //           combined in a fixed order (lane, wave butterfly, LDS, one lane): no atomics and no global scratch, so r_b depends on neither
 //           the batch, the order of execution nor earlier replays of a captured graph.
+//   KNOWN   the known-region overwrite (region in-painting; the arithmetic is defined in include/adm.h), NOT a template parameter: a
+//           runtime branch on p.keep != nullptr, a kernel argument and so uniform over the whole grid, for RESCALE's reason and as the
+//           existing p.mask != nullptr: a template parameter would double the 26 step and the 12 UniPC instantiations for one load and
+//           one compare per float4. After the history is written and before the store and the u8 pack, where the staged mask stands,
+//           every element whose keep byte is non-zero becomes noisy_of(ka, known, kb, known_noise) with (ka, kb) = p.known_table[s]:
+//           add_noise formed by the lane that writes the element, under an arbitrary (H,W) keep mask broadcast over the channels, at
+//           any channel count and width, from three buffers whose size does not depend on the number of steps. sched_known4 and
+//           noisy_of (k_sched_common.h) are the ONE definition for this file, k_unipc.hip and add_noise_kernel. Bytes: +1 B/elem
+//           everywhere for the keep word (one 32-bit load per float4), +8 B/elem where kept (known and known_noise, loaded only where
+//           the keep word is non-zero); with keep == nullptr nothing is read and the arithmetic above is untouched.
 // 26 step instantiations are built: plain and thresholded for the three prediction types, guided or not, with the stream or not (24), and
 // the multistep step for epsilon, guided or not (it has no noise rows); the 13 guided ones carry the rescaled form. The launchers look the
 // kernel up in a table filled at compile time (kStepKernels by (mode, pred, guided, philox), kThresholdKernels by (pred, guided)); a
 // combination that is not built is an empty slot and is refused.
-// The small device helpers (sched_x0, sched_eps, sched_guided*, sched_rescaled*, the mask overwrite, the u8 quantiser / packer) and the
+// The small device helpers (sched_x0, sched_eps, sched_guided*, sched_rescaled*, the two overwrites, the u8 quantiser / packer) and the
 // launch geometry live in k_sched_common.h: the UniPC step (k_unipc.hip, its own kernel template and launcher) shares them bit for bit.
 #include "k_sched_common.h"
 #include <array>
@@ -127,6 +137,8 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
   }
   const float* noise = p.noise + (long)s * p.noise_step_stride;  // per-step slice of a (n_steps,B,C,H,W) noise tensor (0: single step)
   unsigned char* u8 = p.u8_step >= 0 && s != p.u8_step ? nullptr : p.u8;
+  const bool known = p.keep != nullptr;   // KNOWN (a kernel argument: uniform over the grid)
+  const float ka = known ? p.known_table[2 * s] : 0.f, kb = known ? p.known_table[2 * s + 1] : 0.f;
   for (long i = first; i < p.n4; i += stride) {
     const float4 xv = reinterpret_cast<const float4*>(p.x)[i];
     float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
@@ -167,6 +179,7 @@ __device__ __forceinline__ void sched_step_body(const SchedStepParams& p, const 
                   one(xv.w, ev.w, nv.w, hv.w, mv.w)};
     if (MODE == SCHED_MULTISTEP) reinterpret_cast<float4*>(p.hist)[i] = mv;
     if (p.mask != nullptr) sched_mask4(p, s, i, r);
+    if (known) sched_known4(p, ka, kb, i, r);
     reinterpret_cast<float4*>(p.out)[i] = make_float4(r[0], r[1], r[2], r[3]);
     if (u8 != nullptr) reinterpret_cast<unsigned*>(u8)[i] = pack_u8x4(r[0], r[1], r[2], r[3]);
   }
@@ -414,9 +427,7 @@ __global__ void __launch_bounds__(256) encode_step_kernel(float* x, const float*
   }
 }
 
-// sa*x0 + sb*noise: ONE expression for add_noise_kernel and noise_and_velocity_kernel, whose `noisy` must equal add_noise's bit for bit
-__device__ __forceinline__ float noisy_of(float a, float x, float s, float n) { return a * x + s * n; }
-
+// (sa*x0 + sb*noise is noisy_of, k_sched_common.h: ONE expression for the two kernels below and the known-region overwrite of the step)
 __global__ void __launch_bounds__(256) add_noise_kernel(const float* __restrict__ x0, long x0_bstride,
                                                         const float* __restrict__ noise,
                                                         const float* __restrict__ sa, const float* __restrict__ sb,
@@ -546,6 +557,7 @@ int launch_sched_step(const SchedStepParams& in, int mode, hipStream_t st, int p
   const bool guided = p.eps_uncond != nullptr, philox = p.philox != 0;
   ADM_REQUIRE(p.W % 4 == 0, "sched_step: W must be a multiple of 4");
   ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
+  ADM_TRY(sched_known_prepare(p));
   if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_step: the guidance scale must be finite");
   if (philox) {   // noise drawn in the kernel: the key, row offset and stream id from *p.nblock, or from p.nvals when it is null
     ADM_REQUIRE(p.noise == nullptr, "sched_step: a noise buffer and the noise stream exclude each other");

@@ -1,6 +1,6 @@
 // k_sched_common.h — the small device helpers that every scheduler step kernel shares (k_sched.hip, k_unipc.hip): the x0 and noise
-// predictions of the three model types, the guided and rescaled model output, the mask overwrite, the u8 quantiser / packer and the
-// launch geometry. ONE definition each, so that two translation units see the same bits.
+// predictions of the three model types, the guided and rescaled model output, the mask overwrite, the known-region overwrite (with
+// add_noise's one expression, noisy_of), the u8 quantiser / packer and the launch geometry. ONE definition each, so that two translation units see the same bits.
 #pragma once
 #include "adm_kernels.h"
 
@@ -79,6 +79,52 @@ __device__ __forceinline__ void sched_mask4(const SchedStepParams& p, int s, lon
     const int col = col0 + k;
     if (col < p.mask_start || col >= p.W - p.mask_end) r[k] = mrow[k];
   }
+}
+
+// sa*x0 + sb*noise: ONE expression for add_noise_kernel, noise_and_velocity_kernel (whose `noisy` must equal add_noise's bit for bit) and
+// the known-region overwrite (sched_known4). Written out as what add_noise_kernel compiled to for gfx950 under the default contraction
+// when it read `a * x + s * n`: the product s*n rounded on its own, then ONE fused multiply-add of a, x and that product (v_pk_mul_f32,
+// v_pk_fma_f32). The product stands under `fp contract(off)` and feeds nothing but the fmaf, so the bits depend on no contraction setting
+// and on no inlining context.
+__device__ __forceinline__ float noisy_of(float a, float x, float s, float n) {
+#pragma clang fp contract(off)
+  const float sn = s * n;
+  return fmaf(a, x, sn);
+}
+
+// The known-region overwrite (include/adm.h "Region in-painting") of the float4 r of `out` at float4 index i: every element whose keep
+// byte is non-zero becomes noisy_of(ka, known, kb, known_noise), (ka, kb) the row's pair of known_table. keep is (Bm,H,W) bytes without a
+// channel axis: the element index inside the sample, modulo H*W. One 32-bit word of keep per float4 (W % 4 == 0: a float4 never
+// straddles an image row, a channel or a sample), and the two float4 loads only where that word is non-zero: +1 B/elem everywhere,
+// +8 B/elem where kept.
+__device__ __forceinline__ void sched_known4(const SchedStepParams& p, float ka, float kb, long i, float (&r)[4]) {
+  const long e0 = i * 4;
+  const long b = e0 / p.per_sample;
+  const long q = e0 - b * p.per_sample;
+  const unsigned kw = *reinterpret_cast<const unsigned*>(p.keep + b * p.keep_bstride + q % p.plane);
+  if (kw == 0u) return;
+  const float4 kv = *reinterpret_cast<const float4*>(p.known + b * p.known_bstride + q);
+  const float4 nv = reinterpret_cast<const float4*>(p.known_noise)[i];
+  if (kw & 0x000000ffu) r[0] = noisy_of(ka, kv.x, kb, nv.x);
+  if (kw & 0x0000ff00u) r[1] = noisy_of(ka, kv.y, kb, nv.y);
+  if (kw & 0x00ff0000u) r[2] = noisy_of(ka, kv.z, kb, nv.z);
+  if (kw & 0xff000000u) r[3] = noisy_of(ka, kv.w, kb, nv.w);
+}
+
+// The known-region operands of a step (both launchers, after per_sample is derived): the refusals, each by the name of its field, and
+// the two batch strides. keep == NULL: nothing to check, the other five fields are ignored.
+static inline int sched_known_prepare(SchedStepParams& p) {
+  if (p.keep == nullptr) return 0;
+  ADM_REQUIRE(p.known != nullptr && p.known_noise != nullptr, "sched_step: keep needs known and known_noise");
+  ADM_REQUIRE(p.known_table != nullptr, "sched_step: keep needs known_table (two floats per row of coef_table)");
+  ADM_REQUIRE(p.mask == nullptr, "sched_step: keep and mask exclude each other (the known-region overwrite replaces the staged mask)");
+  ADM_REQUIRE(p.B > 0 && p.per_sample > 0 && p.W % 4 == 0, "sched_step: W must be a multiple of 4");
+  ADM_REQUIRE(((uintptr_t)p.keep & 3u) == 0 && ((uintptr_t)p.known & 15u) == 0 && ((uintptr_t)p.known_noise & 15u) == 0,
+              "sched_step: keep must be 4-byte aligned, known and known_noise 16-byte aligned");
+  p.plane = (long)p.H * p.W;
+  p.known_bstride = p.known_batched ? p.per_sample : 0;
+  p.keep_bstride = p.keep_batched ? p.plane : 0;
+  return 0;
 }
 
 static inline int ew_grid(long n4) {

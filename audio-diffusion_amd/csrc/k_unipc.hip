@@ -10,8 +10,8 @@
 // (0 * NaN must not reach the output): last only where c_t != 0, m1 only where c_m1 != 0 || p_m1 != 0, m2 only where c_m2 != 0, and the
 // k_x*x_c product is not formed on a row that ends at sigma = 0 (k_x == 0, x' = m). All four conditions are uniform over the grid.
 // State: last = x_c is written in place (each lane reads then rewrites its own elements), hist is (2,B,C,H,W): row s reads m2 from slot
-// s & 1 and then writes m into that same slot, and reads m1 from slot (s - 1) & 1; no history is ever copied. The mask overwrite goes on
-// `out` alone (the state is the solver's own), then the u8 pack; both are k_sched_common.h's, as are the model-output helpers, so the
+// s & 1 and then writes m into that same slot, and reads m1 from slot (s - 1) & 1; no history is ever copied. The mask overwrite and the
+// known-region overwrite (p.keep != nullptr; k_sched.hip "KNOWN") go on `out` alone (the state is the solver's own), then the u8 pack; both are k_sched_common.h's, as are the model-output helpers, so the
 // bits of m are those of the other step kernels and of the selection (sched_threshold_kernel, launched in front for THRESH).
 // One float4 per lane per iteration, grid-stride, 256 lanes, the grid of sched_step_kernel. Algorithmic traffic on a full row (corrector
 // of order 2): 20 B/elem read (x, o, last, m1, m2) + 12 B/elem written (out, last, m), +4 read when guided; the first row of a run
@@ -37,6 +37,8 @@ __device__ __forceinline__ void unipc_step_body(const SchedStepParams& p, const 
   float4* hist_w = reinterpret_cast<float4*>(p.hist) + (long)(s & 1) * p.n4;              // m2 before the write, m after it
   const float4* hist_1 = reinterpret_cast<const float4*>(p.hist) + (long)((s & 1) ^ 1) * p.n4;   // m1 (slot (s - 1) & 1)
   unsigned char* u8 = p.u8_step >= 0 && s != p.u8_step ? nullptr : p.u8;
+  const bool known = p.keep != nullptr;   // the known-region overwrite (k_sched.hip "KNOWN"): a kernel argument, uniform over the grid
+  const float ka = known ? p.known_table[2 * s] : 0.f, kb = known ? p.known_table[2 * s + 1] : 0.f;
   for (long i = first; i < p.n4; i += stride) {
     const float4 xv = reinterpret_cast<const float4*>(p.x)[i];
     float4 ev = reinterpret_cast<const float4*>(p.eps)[i];
@@ -74,6 +76,7 @@ __device__ __forceinline__ void unipc_step_body(const SchedStepParams& p, const 
     hist_w[i] = mv;
     reinterpret_cast<float4*>(p.last)[i] = cv;
     if (p.mask != nullptr) sched_mask4(p, s, i, r);
+    if (known) sched_known4(p, ka, kb, i, r);
     reinterpret_cast<float4*>(p.out)[i] = make_float4(r[0], r[1], r[2], r[3]);
     if (u8 != nullptr) reinterpret_cast<unsigned*>(u8)[i] = pack_u8x4(r[0], r[1], r[2], r[3]);
   }
@@ -109,6 +112,7 @@ int launch_unipc_step(const SchedStepParams& in, int mode, hipStream_t st, int p
   ADM_REQUIRE(p.philox == 0, "sched_step: noise_source must be 0 with unipc_table (the UniPC step has no noise rows)");
   ADM_REQUIRE(p.B > 0 && p.per_sample > 0 && p.W % 4 == 0, "sched_step: W must be a multiple of 4");
   ADM_REQUIRE(p.mask == nullptr || p.C == 1, "sched_step: mask path requires C == 1 (as in the reference)");
+  ADM_TRY(sched_known_prepare(p));
   if (guided) ADM_REQUIRE(std::isfinite(p.guidance), "sched_step: the guidance scale must be finite");
   if (mode == SCHED_THRESH) {
     ADM_REQUIRE(p.scale != nullptr, "sched_step: the thresholded step needs scale");

@@ -49,6 +49,8 @@ struct adm_unet {
                                  // the plan by the first UniPC loop at this batch size, as eps_uncond_buf is
   adm_unipc_coef* unipc_dev = nullptr;   // per-step adm_unipc_coef of the UniPC loop, beside coef_dev
   int unipc_cap = 0;
+  float* known_dev = nullptr;    // per-step (ka, kb) of the known-region overwrite (include/adm.h "Region in-painting"), beside coef_dev
+  int known_cap = 0;
   // the windowed loop (include/adm.h "Windowed sampling"): the gathered windows (the forwards' input) and the blended model outputs of
   // the wide shape (the step's eps / eps_uncond). Each of eps_buf's size — nW*W >= Wt, so a wide tensor fits where the windows do —
   // allocated with the plan by the first windowed loop at this batch size, as eps_uncond_buf is
@@ -363,6 +365,14 @@ static int ensure_unipc(adm_unet* h, const adm_unipc_coef* unipc_host, int n, hi
   return copy_h2d(h->unipc_dev, unipc_host, sizeof(adm_unipc_coef) * (size_t)n, st);
 }
 
+static int ensure_known(adm_unet* h, const float* known_coef_host, int n, hipStream_t st) {
+  if (h->known_cap < n) {
+    ADM_TRY(dalloc(h, (void**)&h->known_dev, sizeof(float) * 2 * (size_t)n));
+    h->known_cap = n;
+  }
+  return copy_h2d(h->known_dev, known_coef_host, sizeof(float) * 2 * (size_t)n, st);
+}
+
 // adm_sample_loop_args::mode inside this file: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
 // (adm_encode_loop only; adm_sample_loop_ex refuses it)
 enum { LOOP_ENCODE = -1 };
@@ -440,6 +450,10 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
       p.guidance_rescale = a.guidance_rescale; p.rescale = h->rescale_buf;   // (0: off, the buffer is not touched)
     }
     if (a.noise_source == 1) { p.philox = 1; p.nblock = h->noise_blk_dev; }
+    if (a.keep != nullptr) {   // the known-region overwrite: three caller tensors of x's shape (wide when windowed) and the handle's table
+      p.known = a.known; p.known_noise = a.known_noise; p.keep = a.keep; p.known_table = h->known_dev;
+      p.known_batched = a.known_batched != 0; p.keep_batched = a.keep_batched != 0;
+    }
     if (a.unipc_host != nullptr) {   // the UniPC step: two history slots, then last, in the handle's one buffer
       p.unipc_table = h->unipc_dev; p.hist = h->unipc_buf; p.last = h->unipc_buf + 2 * n;
       ADM_TRY(launch_unipc_step(p, a.mode, st, a.prediction));
@@ -480,6 +494,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
   if (a.unipc_host != nullptr) ADM_TRY(ensure_unipc(h, a.unipc_host, a.n_steps, st));
   if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, st));
+  if (a.keep != nullptr) ADM_TRY(ensure_known(h, a.known_coef_host, a.n_steps, st));
   for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
   return 0;
 #else
@@ -496,6 +511,7 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
   if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
   if (a.unipc_host != nullptr) ADM_TRY(ensure_unipc(h, a.unipc_host, a.n_steps, run));
   if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, run));
+  if (a.keep != nullptr) ADM_TRY(ensure_known(h, a.known_coef_host, a.n_steps, run));
   if (!use_graph) {
     for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
   } else {
@@ -529,6 +545,12 @@ static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
       key.push_back(0x500000000ull); key.push_back((uint64_t)a.window_total_w); key.push_back((uint64_t)a.window_stride);
       key.push_back((uint64_t)a.window_wrap); key.push_back((uint64_t)h->win_buf); key.push_back((uint64_t)h->wide_eps_buf);
       key.push_back((uint64_t)h->wide_uncond_buf);
+    }
+    // the known-region overwrite: the three tensors' addresses, the handle's table and the two flags are kernel arguments of the captured
+    // step; what the tensors and the table hold is data behind them (new contents replay the same graph)
+    if (a.keep != nullptr) {
+      key.push_back(0x600000000ull); key.push_back((uint64_t)a.known); key.push_back((uint64_t)a.known_noise); key.push_back((uint64_t)a.keep);
+      key.push_back((uint64_t)h->known_dev); key.push_back((uint64_t)((a.known_batched != 0) | ((a.keep_batched != 0) << 1)));
     }
     if (!h->gexec || key != h->gkey) {
       if (h->gexec) {
@@ -841,6 +863,11 @@ int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* strea
     ADM_REQUIRE(((long)h->cfg.in_channels * h->cfg.sample_h * h->cfg.sample_w) % 4 == 0, "sample_loop: C*H*W must be a multiple of 4");
     for (int i = 0; i < a->n_steps; ++i)   // the counter's third word is the row's timestep as an integer
       ADM_REQUIRE(a->coef_host[i].timestep >= 0.f && a->coef_host[i].timestep < 2147483648.f, "sample_loop: every timestep must be in [0, 2^31)");
+  }
+  if (a->keep != nullptr) {   // the known-region overwrite (include/adm.h "Region in-painting"); NULL: off, the other five fields are ignored
+    ADM_REQUIRE(a->known != nullptr && a->known_noise != nullptr, "sample_loop: keep needs known and known_noise");
+    ADM_REQUIRE(a->known_coef_host != nullptr, "sample_loop: keep needs known_coef_host (n_steps x 2 host floats)");
+    ADM_REQUIRE(a->mask == nullptr, "sample_loop: keep and mask exclude each other (the known-region overwrite replaces the staged mask)");
   }
   if (a->window_total_w != 0) {   // windowed (include/adm.h "Windowed sampling"); 0: off, and window_stride / window_wrap are ignored
     ADM_REQUIRE(a->B > 0, "sample_loop: bad argument");

@@ -276,6 +276,13 @@ typedef struct adm_sched_step_args {
                                 mode 0 (x0 as predicted) or 1 (thresholded, needs scale), mode 2 is refused; noise must be NULL and
                                 noise_source 0 (each refused by name) */
   float* last;               /* the UniPC step: (B,C,H,W) device, the corrected sample of the previous row; read where c_t != 0, always written */
+  const float* known;        /* adm_version() >= 118 ("Region in-painting" below). (Bk,C,H,W) device, Bk = B (known_batched != 0) or 1 */
+  const float* known_noise;  /* (B,C,H,W) device */
+  const uint8_t* keep;       /* NULL: off, and the other five fields are ignored. Otherwise (Bm,H,W) device bytes, Bm = B (keep_batched
+                                != 0) or 1; non-zero: the element is overwritten. Needs known, known_noise and known_table, and mask == NULL
+                                (each refused by name) */
+  const float* known_table;  /* device, two floats (ka, kb) per row of coef_table */
+  int known_batched, keep_batched;
 } adm_sched_step_args;
 int adm_sched_step_ex(const adm_sched_step_args* a, void* stream);
 /* The selection alone (adm_sched_threshold and its _pred / _guided forms): reads x, eps, eps_uncond, guidance_scale, coef_table, step_dev,
@@ -337,6 +344,30 @@ int adm_sched_threshold_ex(const adm_sched_step_args* a, void* stream);
 typedef struct adm_unipc_coef {
   float c_x, c_m1, c_m2, c_t, p_m1;
 } adm_unipc_coef;
+
+/* Region in-painting (adm_version() >= 118): part of the sample is pinned to a known image under an arbitrary keep mask, the noised known
+ * image being formed inside the step kernel instead of being staged per step. THE definition; the kernels (csrc/k_sched.hip "KNOWN",
+ * csrc/k_sched_common.h sched_known4) and the documents refer to it.
+ * Operands (adm_sched_step_args; adm_sample_loop_args has the same with a host table):
+ *   known        (Bk,C,H,W) fp32, Bk = B or 1 (known_batched 0: the one image serves every sample)   the known image, in model space
+ *   known_noise  (B,C,H,W)  fp32                                                                     one fixed draw for all steps
+ *   keep         (Bm,H,W)   bytes, Bm = B or 1 (keep_batched 0: the one mask serves every sample)    no channel axis: broadcast over C
+ *   known_table  two floats (ka, kb) per row of coef_table (the loop: known_coef_host, n_steps x 2 host floats)
+ *   keep must be 4-byte aligned, known and known_noise 16-byte aligned; W % 4 == 0 as everywhere.
+ * Arithmetic, on row s, after the step has formed out (and after the multistep history / the UniPC state, which are the solver's own and
+ * never overwritten, have been written), before the store and the u8 pack: for every element e of sample b with
+ *   keep[b or 0][e mod H*W] != 0:    out = fma(ka, known[b or 0][e], kb * known_noise[b][e]),    (ka, kb) = known_table[s]
+ * the product kb * noise rounded to fp32 on its own, then one fused multiply-add: adm_add_noise's expression, bit for bit (with
+ * ka = sqrt(alphas_cumprod[t]), kb = sqrt(1 - alphas_cumprod[t]) it IS add_noise(known, noise, t)). Elements with keep == 0 are the
+ * step's, bit for bit; keep == NULL is the path of version 117, bit for bit.
+ * The two levels a caller can put into the table (the Python API's `known_level`):
+ *   "current"   row i carries the level of its own timestep t_i, the level the sample had BEFORE the step: the reference's mask rule,
+ *               equal to the staged `mask` path bit for bit; the kept region of the result still carries the noise of the last timestep.
+ *   "previous"  row i carries the level of t_(i+1), the level the sample has AFTER the step, and the last row (1, 0): the kept region
+ *               of the result is the known image exactly (fma(1, known, 0 * noise) = known for finite noise).
+ * Traffic: +1 B/elem for the keep word (one 32-bit load per float4), +8 B/elem where kept. Nothing has a step axis.
+ * Windowed sampling: the three tensors have the wide shape (window_total_w for W) and the overwrite acts on the wide sample.
+ * Refused, each naming the field: keep without known or known_noise; keep without known_table (known_coef_host); keep with mask. */
 
 /* Windowed sampling (adm_version() >= 117): one wide sample denoised jointly through overlapping model-sized windows, the model outputs
  * averaged where windows overlap and ONE scheduler step made on the wide sample (the fusion of Bar-Tal et al. 2023, "MultiDiffusion",
@@ -700,6 +731,11 @@ typedef struct adm_sample_loop_args {
                                 step at W = window_total_w, the counter's increment. The three fields and those buffers' addresses are
                                 part of the captured graph's key: one handle may alternate windowed and ordinary loops. Refused by
                                 name: mask != NULL, and every placement rule (window_total_w, window_stride, window_wrap) */
+  const float* known;        /* adm_version() >= 118: "Region in-painting" above, as adm_sched_step_args; with window_total_w the three */
+  const float* known_noise;  /* tensors have the wide shape. The three pointers, the handle's device copy of the table and the two flags */
+  const uint8_t* keep;       /* are part of the captured graph's key: new contents at the same addresses replay the same graph, and one */
+  const float* known_coef_host;   /* handle may alternate loops with and without it. known_coef_host: n_steps x 2 HOST floats (ka, kb), */
+  int known_batched, keep_batched;   /* row i beside coef_host[i]. keep == NULL: off. Refused by name as in adm_sched_step_ex */
 } adm_sample_loop_args;
 int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
