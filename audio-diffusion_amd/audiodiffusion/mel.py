@@ -212,6 +212,7 @@ class Mel:
         t_w = np.asarray(t_w, np.float64)
         assert len(t_idx) == len(w64)
         pinv = np.ascontiguousarray(np.linalg.pinv(fb64))  # (n_bins, n_mels), librosa.util.nnls start point
+        self.pinv = pinv                                   # the matrix the device holds (tests build their expected product from it)
         wss = _window_sumsquare(window, self.x_res, self.hop_length, n_fft)[n_fft // 2 :][: self.hop_length * (self.x_res - 1)]
         wss = np.ascontiguousarray(wss, np.float32)
         nnls_cols = max((2**8 * 2**10) // (self.n_mels * 8), 1)  # librosa MAX_MEM_BLOCK column blocking

@@ -839,6 +839,9 @@ static int upload(adm_mel* h, T** dst, const T* src, size_t n) {
 
 static size_t fft_smem(const adm_mel* h) { return sizeof(double) * 2 * (size_t)h->cfg.n_fft + sizeof(double) * (h->n_bins + 3); }
 
+// what the last forward launch on this thread ran (include/adm.h: adm_mel_last_variant; tests assert the launcher's rules with it)
+static thread_local int g_mel_last_variant = 0;
+
 }  // namespace adm
 
 using namespace adm;
@@ -950,8 +953,10 @@ static int mel_forward_power_impl(adm_mel_t* h, const void* audio, int is_f64, i
     if (is_f64) { if (occ == 2) ADM_MEL_FAST_LAUNCH(double, 2); else ADM_MEL_FAST_LAUNCH(double, 1); }
     else { if (occ == 2) ADM_MEL_FAST_LAUNCH(float, 2); else ADM_MEL_FAST_LAUNCH(float, 1); }
 #undef ADM_MEL_FAST_LAUNCH
+    g_mel_last_variant = 200 + (int)tsz * 10 + occ;
     return ADM_CHECK_LAUNCH();
   }
+  g_mel_last_variant = 100 + (is_f64 ? 8 : 4) * 10 + 1;
   if (is_f64) {
     ADM_LAUNCH((mel_stft_power_kernel<double>), grid, dim3(256), smem, st, (const double*)audio, slice_stride, n_samples,
                c.n_fft, h->log2n, c.hop_length, h->window, (const double2*)h->twiddle, h->fb_start, h->fb_count,
@@ -1132,5 +1137,8 @@ int adm_mel_last_nnls(adm_mel_t* h, float* pg_start, int* iterations) {
   *iterations = h->last_iters;
   return 0;
 }
+
+// Test aid: engine * 100 + element size * 10 + waves per SIMD of the last forward launch on this thread (include/adm.h).
+int adm_mel_last_variant(void) { return g_mel_last_variant; }
 
 }  // extern "C"

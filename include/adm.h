@@ -70,7 +70,7 @@ int adm_has_experiments(void);
  *   on a second stream beside those ops (scheduling only: bit-identical results; adm_plan_op.hoist_from shows where) | 0 every op in list
  *   order on the caller's stream | -1 ADM_SIDE_OVERLAP. Every net re-plans on its next call (a UNet's captured loop is re-captured).
  * The dispatch epoch moves only when a value really changes; set options BEFORE adm_unet_refresh_weights / the next train step.
- * adm_version() = 108 (option "wgrad_path", test aids adm_last_wgrad_variant, adm_wgrad_reduce); 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
+ * adm_version() = 119 (test aid adm_mel_last_variant); 108 (option "wgrad_path", test aids adm_last_wgrad_variant, adm_wgrad_reduce); 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
 int adm_set_option(const char* name, int value);
 /* Per-(device, stream) scratch the library keeps for a stream (the split-K slab buffer of the small-plane convolutions, >= 1 MiB, at most
  * 1024 streams per device): give it back BEFORE destroying a stream that has run library calls. Drains the stream first (a captured graph of
@@ -927,6 +927,13 @@ int adm_mel_set_nnls_solver(adm_mel_t* h, double lipschitz, int max_iter);
 /* after an adm_mel_inverse with pg_max_host != NULL (which then holds the projected gradient of the RETURNED point):
  * the start point's max |projected gradient| and the largest iteration count any column needed. */
 int adm_mel_last_nnls(adm_mel_t* h, float* pg_start, int* iterations);
+/* Test aid (adm_version() >= 119; tests assert the forward launcher's rules with it): what the last adm_mel_forward /
+ * adm_mel_forward_power on this thread launched, engine * 100 + element size * 10 + waves per SIMD. Engine 1 = radix-2 in LDS, one frame
+ * per workgroup of four waves (mel_stft_power_kernel, any n_fft) | 2 = wave per frame, radix 16 (mel_stft2048_kernel, n_fft = 2048 unless
+ * ADM_MEL_FAST=0); element size 4 = fp32 audio, 8 = fp64; waves per SIMD 1 or 2 (engine 2: 2 unless ADM_MEL_OCC=1 or the eight-wave LDS
+ * image exceeds 160 KiB). E.g. 141 = mel_stft_power_kernel<float>, 282 = mel_stft2048_kernel<double, 2>. 0 before the first launch; a
+ * call that returns an error before launching leaves the value as it was. */
+int adm_mel_last_variant(void);
 
 #ifdef __cplusplus
 }
