@@ -115,6 +115,9 @@ _SIGS = {
     "adm_last_error": (C.c_char_p, []),
     "adm_is_device_build": (C.c_int, []),
     "adm_last_conv_variant": (C.c_int, []),
+    "adm_last_conv_detail": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "adm_conv2d_gn_finish": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_int), C.c_void_p]),
     "adm_last_attention_variant": (C.c_int, []),
     "adm_release_stream": (C.c_int, [C.c_void_p]),
     "adm_has_experiments": (C.c_int, []),

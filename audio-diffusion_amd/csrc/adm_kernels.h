@@ -88,6 +88,11 @@ void conv_out_dims(int H, int W, int up, int stride, int ks, int pad_lo, int* Ho
 // 1000 + ... for the direct small-channel kernels (profiling only).
 int last_conv_variant();
 void set_last_conv_variant(int v);
+// what the last fp32 implicit-GEMM / small-channel launch on this thread chose beyond the variant (include/adm.h: adm_last_conv_detail has
+// the slots; tests assert the launchers' rules with it). `variant` is the variant the record belongs to: a launch of another family
+// (Winograd, bf16) changes last_conv_variant() only, and the record then reads as stale.
+struct ConvDetail { int variant, bm, split, finish, tap_mask, TW, TH, NI, kpf, zparts; };
+ConvDetail& last_conv_detail();
 // GroupNorm of a convolution's OUTPUT folded into its split-K finish pass (k_groupnorm.hip: ksplit_finish_gn_kernel). The executor
 // announces the GroupNorm that reads the tensor before launch_conv2d (request), the split-K launchers honour it when they can
 // (pending -> launch_ksplit_finish_gn) and the executor then skips its statistics launch (taken). Thread-local like the variant.

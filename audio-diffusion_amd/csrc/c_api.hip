@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 119; }   // 118: adm_sched_step_args.known / .known_noise / .keep / .known_table / .known_batched / .keep_batched, adm_sample_loop_args the same with .known_coef_host (region in-painting: the known-region overwrite under an arbitrary keep mask inside the step kernels, csrc/k_sched_common.h sched_known4; no new symbol); 117: adm_window_gather / adm_window_blend, adm_sample_loop_args.window_total_w / .window_stride / .window_wrap (windowed sampling: wide and circular spectrograms through overlapping model-sized windows in the captured loop, csrc/k_window.hip; no new loop symbol); 116: adm_unipc_coef, adm_sched_step_args.unipc_table / .last, adm_sample_loop_args.unipc_host (the UniPC predictor-corrector step and loop, csrc/k_unipc.hip; no new symbol); 115: adm_sched_step_args.guidance_rescale / .rescale, adm_sample_loop_args.guidance_rescale (rescaled classifier-free guidance; no new symbol); 114: adm_sched_step_args / adm_sample_loop_args and adm_sched_step_ex / adm_sched_threshold_ex / adm_sample_loop_ex (one struct-argument entry point per family; the positional ones are frozen); 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 120; }   // 120: test aids adm_conv2d_gn_finish (a convolution announced as the executors announce it when a GroupNorm reads its output) and adm_last_conv_detail (what the fp32 implicit-GEMM / small-channel launchers chose: cout tile, split, finish kernel, tap mask, pixel tile); 119: test aid adm_mel_last_variant; 118: adm_sched_step_args.known / .known_noise / .keep / .known_table / .known_batched / .keep_batched, adm_sample_loop_args the same with .known_coef_host (region in-painting: the known-region overwrite under an arbitrary keep mask inside the step kernels, csrc/k_sched_common.h sched_known4; no new symbol); 117: adm_window_gather / adm_window_blend, adm_sample_loop_args.window_total_w / .window_stride / .window_wrap (windowed sampling: wide and circular spectrograms through overlapping model-sized windows in the captured loop, csrc/k_window.hip; no new loop symbol); 116: adm_unipc_coef, adm_sched_step_args.unipc_table / .last, adm_sample_loop_args.unipc_host (the UniPC predictor-corrector step and loop, csrc/k_unipc.hip; no new symbol); 115: adm_sched_step_args.guidance_rescale / .rescale, adm_sample_loop_args.guidance_rescale (rescaled classifier-free guidance; no new symbol); 114: adm_sched_step_args / adm_sample_loop_args and adm_sched_step_ex / adm_sched_threshold_ex / adm_sample_loop_ex (one struct-argument entry point per family; the positional ones are frozen); 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -89,6 +89,14 @@ int adm_set_option(const char* name, int value) {
   return 0;
 }
 int adm_last_conv_variant(void) { return adm::last_conv_variant(); }
+int adm_last_conv_detail(int* out, int n) {
+  const adm::ConvDetail d = adm::last_conv_detail();
+  const int v = adm::last_conv_variant();
+  const bool fresh = d.variant == v && v != 0;       // (a Winograd / bf16 launch since: only the variant is known)
+  const int slots[ADM_CONV_DETAIL_SLOTS] = {v, d.bm, d.split, d.finish, d.tap_mask, d.TW, d.TH, d.NI, d.kpf, d.zparts};
+  for (int i = 0; out != nullptr && i < n; ++i) out[i] = i >= ADM_CONV_DETAIL_SLOTS ? 0 : ((i == 0 || fresh) ? slots[i] : 0);
+  return v;
+}
 int adm_last_attention_variant(void) { return adm::last_attention_variant(); }
 int adm_release_stream(void* stream) { adm::conv_ksplit_release((hipStream_t)stream); return 0; }
 int adm_has_experiments(void) { return 0; }   // (kept for ABI stability: the experiments builds were retired in round 6)
@@ -316,6 +324,17 @@ int adm_groupnorm_finalize(const double* stats1, int C1, int tiles1, const doubl
 int adm_conv2d(const adm_conv_args* a, void* stream) {
   ADM_REQUIRE(a && a->x1 && a->wpacked && a->out, "conv2d: null argument");
   return launch_conv2d(*a, (hipStream_t)stream);
+}
+// Test aid (adm_version() >= 120): adm_conv2d announced to the launchers the way the executors announce it when a GroupNorm reads `out` next.
+int adm_conv2d_gn_finish(const adm_conv_args* a, const float* gamma, const float* beta, int groups, float eps, float* scale, float* shift,
+                         int* taken, void* stream) {
+  ADM_REQUIRE(a && a->x1 && a->wpacked && a->out && gamma && beta && scale && shift && groups > 0, "conv2d_gn_finish: null argument");
+  const GnFuse f = {gamma, beta, eps, groups, scale, shift, nullptr};
+  conv_gn_fuse_request(&f);
+  const int rc = launch_conv2d(*a, (hipStream_t)stream);
+  if (taken != nullptr) *taken = conv_gn_fuse_taken() ? 1 : 0;
+  conv_gn_fuse_request(nullptr);
+  return rc;
 }
 
 int adm_pack_conv_weight(const float* w, float* wpacked, int Cout, int Cin, int ks, void* stream) {

@@ -603,6 +603,10 @@ void conv_out_dims(int H, int W, int up, int stride, int ks, int pad_lo, int* Ho
 static thread_local int g_last_variant = 0;
 int last_conv_variant() { return g_last_variant; }
 void set_last_conv_variant(int v) { g_last_variant = v; }
+static thread_local ConvDetail g_last_detail = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+ConvDetail& last_conv_detail() { return g_last_detail; }
+// finish kernels as adm_last_conv_detail reports them
+enum { FIN_NONE = 0, FIN_VEC4 = 1, FIN_SCALAR = 2, FIN_GN = 3 };
 
 static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
@@ -883,8 +887,11 @@ static int launch_ksplit(const ConvParams& p, int bm, int S, hipStream_t st) {
     allow_big_lds(conv_mfma_pf_kernel<KS, 1, 1, true>, smem);
     ADM_LAUNCH((conv_mfma_pf_kernel<KS, 1, 1, true>), dim3(q.nblk), dim3(256), smem, st, q);
   }
-  if (const GnFuse* f = conv_gn_fuse_pending(p.Cout))
+  g_last_detail.bm = bm; g_last_detail.split = S; g_last_detail.finish = FIN_VEC4;
+  if (const GnFuse* f = conv_gn_fuse_pending(p.Cout)) {
+    g_last_detail.finish = FIN_GN;
     return launch_ksplit_finish_gn(scratch, S, total, p.bias, p.chan_add, p.chan_add_stride, p.residual, p.out, p.N, p.Cout, p.Ho * p.Wo, *f, st);
+  }
   long g = (total / 4 + 255) / 256;
   if (g > 4096) g = 4096;
   ADM_LAUNCH(ksplit_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, (const float*)scratch, S, total, p.bias, p.chan_add,
@@ -918,7 +925,7 @@ static int dispatch_pf(const ConvParams& p, int bm, hipStream_t st) {
     while (S > 1 && nch / S < 4) --S;
     if (S > 1) {
       const int rc = launch_ksplit<KS>(p, bm2, S, st);
-      if (rc <= 0) { if (rc == 0) g_last_variant += 5; return rc; }      // 2316: the split-K instantiation
+      if (rc <= 0) { if (rc == 0) { g_last_variant += 5; g_last_detail.variant = g_last_variant; } return rc; }      // 2316: the split-K instantiation
     }
   }
   if (bm == 128) {
@@ -1005,8 +1012,13 @@ static int launch_ksplit_generic(const ConvParams& p, hipStream_t st) {
   }
   const int HW = p.Ho * p.Wo;
   g_last_variant = KS * 100 + STRIDE * 10 + bm / 32 + 5;      // x16 / x26 + ...: 3x3 stride 1 -> 316 / 317 / 319 (bm 32 / 64 / 128)
-  if (const GnFuse* f = big ? nullptr : conv_gn_fuse_pending(p.Cout))      // (one workgroup per (group, sample) is a small-plane design)
+  g_last_detail.variant = g_last_variant; g_last_detail.bm = bm; g_last_detail.split = S; g_last_detail.tap_mask = q.tap_mask;
+  g_last_detail.kpf = (bm == 128 && STRIDE == 1 && kpf) ? 1 : 0;
+  g_last_detail.finish = HW % 4 == 0 ? FIN_VEC4 : FIN_SCALAR;
+  if (const GnFuse* f = big ? nullptr : conv_gn_fuse_pending(p.Cout)) {      // (one workgroup per (group, sample) is a small-plane design)
+    g_last_detail.finish = FIN_GN;
     return launch_ksplit_finish_gn(scratch, S, total, p.bias, p.chan_add, p.chan_add_stride, p.residual, p.out, p.N, p.Cout, HW, *f, st);
+  }
   if (HW % 4 == 0) {
     long g = (total / 4 + 255) / 256;
     if (g > 4096) g = 4096;
@@ -1106,8 +1118,9 @@ int launch_conv2d(const adm_conv_args& a, hipStream_t st) {
   p.nblk = n_pt * p.n_ct;
   const size_t smem = sizeof(float) * ((size_t)CK * p.CS + (size_t)CK * a.ks * a.ks * bm);
   g_last_variant = a.ks * 100 + a.stride * 10 + bm / 32;
+  g_last_detail = ConvDetail{g_last_variant, bm, 1, FIN_NONE, 0x1ff, TW, TH, NI, 0, 1};
   if (use_pf() && a.stride == 1 && a.ks == 3 && p.CS <= 256) {
-    g_last_variant += 2000;
+    g_last_variant += 2000; g_last_detail.variant = g_last_variant;
     return dispatch_pf<3>(p, bm, st);
   }
   // (1x1 on planes of <= 4x4 pixels with >= 64 input channels: the split generic kernel — the pipelined one has no split for 1x1, and a
@@ -1115,7 +1128,7 @@ int launch_conv2d(const adm_conv_args& a, hipStream_t st) {
   static const int small1x1 = [] { const char* e = getenv("ADM_KSP_1X1_SMALL"); return e ? atoi(e) : 1; }();     // developer A/B
   const bool split_1x1 = small1x1 && a.ks == 1 && p.Ho * p.Wo <= 16 && Ct / CK >= 8 && a.w_bstride == 0;
   if (!split_1x1 && use_pf() && a.ks == 1 && p.CS == 128 && Ct % 32 == 0 && a.C1 % 32 == 0 && TW % 4 == 0 && p.Wo % 4 == 0 && a.W % 4 == 0) {
-    g_last_variant += 2000;
+    g_last_variant += 2000; g_last_detail.variant = g_last_variant;
     return dispatch_pf<1>(p, bm, st);
   }
   if (a.ks == 3 && a.stride == 1) return dispatch_bm<3, 1>(p, bm, smem, st);

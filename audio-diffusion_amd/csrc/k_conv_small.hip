@@ -363,7 +363,13 @@ int launch_conv_small(const adm_conv_args& a, hipStream_t st) {
   ADM_REQUIRE(a.x2 == nullptr || a.C2 == 0, "conv_small: virtual concat not supported");
   ADM_REQUIRE(a.stride == 1 && !a.up, "conv_small: stride 1, no upsample only");
   ADM_REQUIRE(a.chan_add == nullptr, "conv_small: chan_add not supported");
+  // (these kernels index dense tensors and one weight image: a slice or per-sample weights would be read as something else, silently)
+  ADM_REQUIRE((a.x1_bstride == 0 || a.x1_bstride == (long)a.C1 * a.H * a.W) && a.w_bstride == 0,
+              "conv_small: batch strides (channel slices, per-sample weights) not supported");
   set_last_conv_variant(a.C1 <= 4 ? 1001 : 1002);
+  // (bm: which of the four kernels — 1 conv_small_cin_kernel, 2 conv_small_cin_wide_kernel, 3 conv_small_cout_wide_kernel, 4 conv_small_cout_kernel)
+  ConvDetail& det = last_conv_detail();
+  det = ConvDetail{a.C1 <= 4 ? 1001 : 1002, 0, 1, 0, 0x1ff, 0, 0, 1, 0, 1};
   if (a.C1 <= 4) {
     ADM_REQUIRE(a.gn_scale == nullptr && !a.act, "conv_small(cin): no fused norm/activation");
     ADM_REQUIRE(a.ks == 3 || a.ks == 1, "conv_small: ks");
@@ -372,6 +378,7 @@ int launch_conv_small(const adm_conv_args& a, hipStream_t st) {
       dim3 gw((unsigned)((HW / 4 + 255) / 256), a.N, 1);
       while ((long)gw.x * gw.y * gw.z < 256 && gw.z < 16 && a.Cout / (int)(2 * gw.z) >= 8) gw.z *= 2;
       ADM_REQUIRE(a.stats_out == nullptr || a.stats_tiles == (int)gw.x * 4, "conv_small(cin): stats_tiles mismatch");
+      det.bm = 2; det.TW = 1024; det.TH = 1; det.zparts = (int)gw.z;
 #define ADM_CINW_CASE(CI)                                                                                          \
   if (a.C1 == CI) {                                                                                                \
     ADM_LAUNCH((conv_small_cin_wide_kernel<CI>), gw, dim3(256), 0, st, a.x1, a.N, a.H, a.W, a.wpacked, a.bias,      \
@@ -383,6 +390,7 @@ int launch_conv_small(const adm_conv_args& a, hipStream_t st) {
     }
     ADM_REQUIRE(a.stats_out == nullptr, "conv_small(cin): this variant has no statistics epilogue");
     dim3 grid((unsigned)((HW + 255) / 256), a.N), block(256);
+    det.bm = 1; det.TW = 256; det.TH = 1;
 #define ADM_CIN_CASE(CI, KK)                                                                                       \
   if (a.C1 == CI && a.ks == KK) {                                                                                  \
     ADM_LAUNCH((conv_small_cin_kernel<CI, KK>), grid, block, 0, st, a.x1, a.N, a.H, a.W, a.wpacked, a.bias, a.Cout, \
@@ -400,6 +408,7 @@ int launch_conv_small(const adm_conv_args& a, hipStream_t st) {
   const bool single_split = conv_single_sample(a) && a.C1 >= 64;
   if (a.W % 64 == 0 && a.H % 16 == 0 && use_wide_cout() && !single_split) {   // whole 64 x 16 tiles: the wide kernel (16-byte aligned rows)
     const int wx = a.W / 64, wy = a.H / 16;
+    det.bm = 3; det.TW = 64; det.TH = 16;
 #define ADM_COUTW_CASE(CO)                                                                                              \
   if (a.Cout == CO) {                                                                                                   \
     ADM_LAUNCH((conv_small_cout_wide_kernel<CO>), dim3(wx * wy, a.N), dim3(256), 0, st, a.x1, a.C1, a.N, a.H, a.W,      \
@@ -410,6 +419,7 @@ int launch_conv_small(const adm_conv_args& a, hipStream_t st) {
 #undef ADM_COUTW_CASE
   }
   const int tiles_x = ceil_div(a.W, 16), tiles_y = ceil_div(a.H, 16);
+  det.bm = 4; det.TW = 16; det.TH = 16;
   // planes of at most 32x32 pixels (a function of the layer, not of the batch: the partition fixes the summation order): the channel
   // loop split over 8 workgroups per tile
   int S = 1;
@@ -425,6 +435,7 @@ int launch_conv_small(const adm_conv_args& a, hipStream_t st) {
   if (a.Cout == CO) {                                                                                              \
     ADM_LAUNCH((conv_small_cout_kernel<CO>), dim3(tiles_x * tiles_y, a.N, S), dim3(256), 0, st, a.x1, a.C1, a.N, a.H, \
                a.W, a.gn_scale, a.gn_shift, a.act, a.wpacked, a.bias, a.residual, a.out, tiles_x, part, total);   \
+    if (part != nullptr) { det.split = S; det.finish = (a.H * a.W) % 4 == 0 ? 1 : 2; }  /* (this launcher's record: adm_last_conv_detail) */ \
     if (part != nullptr)                                                                                           \
       return launch_ksplit_finish(part, S, total, a.bias, nullptr, 0, a.residual, a.out, a.Cout, a.H * a.W, st);   \
     return ADM_CHECK_LAUNCH();                                                                                     \

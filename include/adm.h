@@ -70,7 +70,7 @@ int adm_has_experiments(void);
  *   on a second stream beside those ops (scheduling only: bit-identical results; adm_plan_op.hoist_from shows where) | 0 every op in list
  *   order on the caller's stream | -1 ADM_SIDE_OVERLAP. Every net re-plans on its next call (a UNet's captured loop is re-captured).
  * The dispatch epoch moves only when a value really changes; set options BEFORE adm_unet_refresh_weights / the next train step.
- * adm_version() = 119 (test aid adm_mel_last_variant); 108 (option "wgrad_path", test aids adm_last_wgrad_variant, adm_wgrad_reduce); 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
+ * adm_version() = 120 (test aids adm_last_conv_detail, adm_conv2d_gn_finish); 119 (test aid adm_mel_last_variant); 108 (option "wgrad_path", test aids adm_last_wgrad_variant, adm_wgrad_reduce); 107 (test aids adm_time_embedding, adm_temb_proj); 106 (adm_last_attention_variant); 105 (option "side_overlap"; adm_plan_op, adm_unet_plan_ops, adm_vae_plan_ops); 104 since round 6 (adm_conv_args.single_sample, option "single_sample"; 103: adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream); 102 since round 5 (Winograd filter buffers hold two images: adm_winograd_packed_floats); 101 since round 4 (adm_slerp_grid takes DOUBLE weights since round 3; blocked-image entry points). */
 int adm_set_option(const char* name, int value);
 /* Per-(device, stream) scratch the library keeps for a stream (the split-K slab buffer of the small-plane convolutions, >= 1 MiB, at most
  * 1024 streams per device): give it back BEFORE destroying a stream that has run library calls. Drains the stream first (a captured graph of
@@ -78,6 +78,22 @@ int adm_set_option(const char* name, int value);
 int adm_release_stream(void* stream);
 /* Kernel variant the last adm_conv2d on this thread dispatched to (see adm_op_profile.variant; 4311 = Winograd). */
 int adm_last_conv_variant(void);
+/* Test aid (adm_version() >= 120; tests assert the forward launchers' rules with it): what the last adm_conv2d on this thread chose, for the
+ * fp32 implicit-GEMM kernels (variants 1xx / 3xx / 21xx / 23xx) and the small-channel kernels (1001 / 1002). Fills out[0 .. n - 1] (slots
+ * beyond ADM_CONV_DETAIL_SLOTS read 0) and returns the variant. After a launch of another family (Winograd, 16-bit operands) only slot 0 is
+ * known and the others read 0; a call that returns an error before it launches may leave a partial record.
+ *   [0] variant (= adm_last_conv_variant)
+ *   [1] cout tile of the MFMA kernel that ran (32 / 64 / 128; the split-K instantiations choose their own). Small-channel family: the kernel,
+ *       1 conv_small_cin_kernel | 2 conv_small_cin_wide_kernel | 3 conv_small_cout_wide_kernel | 4 conv_small_cout_kernel
+ *   [2] parts of the K (input channel) split, 1 = unsplit
+ *   [3] finish kernel of a split launch: 0 none | 1 ksplit_finish_kernel (four pixels per thread) | 2 ksplit_finish1_kernel | 3 the
+ *       GroupNorm-fused finish (ksplit_finish_gn_kernel)
+ *   [4] tap mask of the split generic kernel (bit ty * 3 + tx; 0x1ff everywhere else)
+ *   [5] [6] pixel tile TW, TH (small-channel family: the pixels one workgroup covers, as a row x column shape)   [7] images per tile NI
+ *   [8] 1 = the register-pipelined instantiation of the split generic kernel (ADM_KSP_PIPE)
+ *   [9] cout parts of conv_small_cin_wide_kernel's grid (1 elsewhere) */
+#define ADM_CONV_DETAIL_SLOTS 10
+int adm_last_conv_detail(int* out, int n);
 /* Kernel family the last attention entry point on this thread launched (adm_version() >= 106; tests assert the dispatch rules with it):
  * family * 100 + head_dim, families 1 = one pass, whole head in LDS (attention_kernel) | 2 = four lanes per query (attention_split4_kernel,
  * "single_sample") | 3 = key blocks, online softmax on the vector ALUs (attention_blocked_kernel) | 4 = flash form on the f32 MFMAs
@@ -470,6 +486,14 @@ int adm_groupnorm_finalize(const double* stats1, int C1, int tiles1, const doubl
                            int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift,
                            void* stream);
 int adm_conv2d(const adm_conv_args* a, void* stream);
+/* Test aid (adm_version() >= 120): adm_conv2d announced the way the executors announce a convolution whose output a GroupNorm (gamma, beta:
+ * Cout floats; groups; eps) reads next. Where a launcher honours the announcement and option "gn_fuse_finish" is on, the launch's finish
+ * pass leaves that GroupNorm's scale / shift (N x Cout floats each, as adm_groupnorm_stats) and *taken = 1; otherwise the call is adm_conv2d,
+ * scale / shift are not written and *taken = 0. `out` is bit-identical either way. The launchers that honour it: the split-K launches of the
+ * fp32 implicit-GEMM kernels on planes of at most 8x8 pixels (with "conv_wino" = 0 and "conv_bf16" = 0 the only ones) and, where they run,
+ * the split Winograd launch of the single-sample rule and the blocked 16-bit route: *taken reports whichever of them took it. */
+int adm_conv2d_gn_finish(const adm_conv_args* a, const float* gamma, const float* beta, int groups, float eps, float* scale, float* shift,
+                         int* taken, void* stream);
 /* (Cout,Cin,ks,ks) -> [Cin][ks*ks][Cout]; both device pointers. */
 int adm_pack_conv_weight(const float* w, float* wpacked, int Cout, int Cin, int ks, void* stream);
 /* Backward-data form: (Cout,Cin,ks,ks) -> [Cout][ks*ks][Cin] (channel-transposed, spatially flipped). Feeding it to
