@@ -72,12 +72,19 @@ def outpaint(pipe, raw_audio: np.ndarray, n_segments: int, overlap_secs: float, 
     return track, images
 
 
+def _cell(pipe) -> int:
+    """Image columns per column of the tensor the pipeline denoises: 1, or f = 2^(VAE blocks - 1) for a latent pipeline, whose `frames`,
+    `window_stride` and `keep_mask` count latent cells."""
+    return pipe._vae_factor() if getattr(pipe, "vqvae", None) is not None else 1
+
+
 def long_placement(pipe, seconds: float, overlap_secs: float, circular: bool = False) -> Tuple[int, int]:
     """`seconds` of audio and `overlap_secs` of overlap between neighbouring windows, as the (frames, window_stride) of windowed sampling
     (include/adm.h "Windowed sampling") for this pipeline's model width W and Mel settings; one column is hop_length / sample_rate
     seconds. Rounded to the placement rules: the stride W - overlap to the nearest multiple of 4 in [4, W]; the number of windows up, so
-    that the clip is at least `seconds` long (frames = W + k*stride open, k*stride >= W circular)."""
-    cols_per_sec = pipe.mel.get_sample_rate() / pipe.mel.hop_length
+    that the clip is at least `seconds` long (frames = W + k*stride open, k*stride >= W circular). With a `vqvae` both are in latent
+    columns (f image columns each, so one is f * hop_length / sample_rate seconds) and W is the latent UNet's width."""
+    cols_per_sec = pipe.mel.get_sample_rate() / pipe.mel.hop_length / _cell(pipe)
     W = pipe.unet._hw()[1]
     stride = int(round((W - overlap_secs * cols_per_sec) / 4)) * 4
     stride = min(max(stride, 4), W)
@@ -95,7 +102,7 @@ def generate_long(pipe, seconds: float, overlap_secs: float, circular: bool = Fa
     does not). Returns (result of the pipeline call, dict(frames, window_stride, seconds, overlap_secs)): the values as rounded to the
     placement rules (`long_placement`), in columns and back in seconds. `call`: further keywords of the pipeline call."""
     frames, stride = long_placement(pipe, seconds, overlap_secs, circular)
-    secs_per_col = pipe.mel.hop_length / pipe.mel.get_sample_rate()
+    secs_per_col = _cell(pipe) * pipe.mel.hop_length / pipe.mel.get_sample_rate()
     used = dict(frames=frames, window_stride=stride, seconds=frames * secs_per_col,
                 overlap_secs=(pipe.unet._hw()[1] - stride) * secs_per_col)
     return pipe(frames=frames, window_stride=stride, circular=circular, **call), used
@@ -104,15 +111,18 @@ def generate_long(pipe, seconds: float, overlap_secs: float, circular: bool = Fa
 def span_keep_mask(pipe, spans_secs: Sequence[Tuple[float, float]], width: int = None) -> np.ndarray:
     """The (H, W) uint8 keep mask that regenerates the time spans `spans_secs` [(from, to), ...] and keeps everything else: seconds
     become columns by the pipeline's own rule for `mask_start_secs` (pixels_per_second = W * sample_rate / x_res / hop_length,
-    truncated), each span covering columns [int(from * pps), int(to * pps)). `width`: the mask's width (default: the model's W)."""
+    truncated), each span covering columns [int(from * pps), int(to * pps)). `width`: the mask's width (default: the model's W).
+    With a `vqvae` the mask has the latent's resolution (`width` in latent columns): the spans are laid out in image columns as above
+    (f per latent column) and a latent column is kept only if all f image columns under it are kept."""
     H, W = pipe.unet._hw()
-    pps = W * pipe.mel.get_sample_rate() / pipe.mel.x_res / pipe.mel.hop_length
-    keep = np.ones((H, W if width is None else int(width)), dtype=np.uint8)
+    f = _cell(pipe)
+    pps = f * W * pipe.mel.get_sample_rate() / pipe.mel.x_res / pipe.mel.hop_length
+    keep = np.ones((H, f * (W if width is None else int(width))), dtype=np.uint8)
     for a, b in spans_secs:
         if not 0 <= a <= b:
             raise ValueError(f"spans_secs: a span is (from, to) with 0 <= from <= to, not {(a, b)}")
         keep[:, int(a * pps):int(b * pps)] = 0
-    return keep
+    return keep if f == 1 else np.ascontiguousarray(keep.reshape(H, -1, f).min(axis=2))
 
 
 @torch.no_grad()
@@ -129,14 +139,16 @@ def inpaint(pipe, raw_audio: np.ndarray, spans_secs: Sequence[Tuple[float, float
 def continue_track(pipe, raw_audio: np.ndarray, seconds: float, overlap_secs: float, **call):
     """Continue `raw_audio` to a clip of about `seconds` in ONE windowed pipeline call: the wide sample of `long_placement(pipe,
     seconds, overlap_secs)` is denoised jointly through overlapping windows, the columns the input covers (hop_length samples each, from
-    column 0) are kept and the rest is generated. The one-call counterpart of `outpaint`, which runs the whole pipeline once per
+    column 0; with a `vqvae` f * hop_length samples per latent column, and only columns the input covers whole) are kept and the rest is
+    generated. The one-call counterpart of `outpaint`, which runs the whole pipeline once per
     segment at batch 1. Returns (result of the pipeline call, dict(frames, window_stride, kept_columns, seconds)). `call`: further
     keywords of the pipeline call."""
     frames, stride = long_placement(pipe, seconds, overlap_secs)
-    kept = min(frames, int(len(raw_audio) / pipe.mel.hop_length))
+    kept = min(frames, int(len(raw_audio) / (_cell(pipe) * pipe.mel.hop_length)))
     keep = np.zeros((pipe.unet._hw()[0], frames), dtype=np.uint8)
     keep[:, :kept] = 1
-    used = dict(frames=frames, window_stride=stride, kept_columns=kept, seconds=frames * pipe.mel.hop_length / pipe.mel.get_sample_rate())
+    used = dict(frames=frames, window_stride=stride, kept_columns=kept,
+                seconds=frames * _cell(pipe) * pipe.mel.hop_length / pipe.mel.get_sample_rate())
     return pipe(raw_audio=raw_audio, keep_mask=keep, frames=frames, window_stride=stride, **call), used
 
 

@@ -129,6 +129,24 @@ def window_blend(windows, total_w, stride, wrap=False):
     return out
 
 
+def window_crossfade(windows, total_w, stride, wrap=False, want_u8=False):
+    """windows (B*nW, C, H, W), as `window_gather` lays them out -> (B, C, H, total_w): per column the weighted mean of the windows that
+    cover it, each window's integer weight falling to 1 towards every edge that has a neighbour; a column one window covers is that
+    window's value, copied (include/adm.h "Tiled codec"; csrc/k_window.hip). The join of a tiled codec's windows, where `window_blend`
+    is the fusion of model outputs inside a step. want_u8: -> (out, u8), u8 (B, C, H, total_w) the bytes `dequant_u8(out)` gives,
+    written by the same kernel."""
+    _f32(windows)
+    BW, Cc, H, W = windows.shape
+    nW = window_count(total_w, W, stride, wrap)
+    if BW % nW:
+        raise ValueError(f"{BW} windows are not a multiple of the {nW} windows per sample of total_w={total_w}, stride={stride}, wrap={wrap}")
+    out = torch.empty((BW // nW, Cc, H, int(total_w)), dtype=torch.float32, device=windows.device)
+    u8 = torch.empty(out.shape, dtype=torch.uint8, device=windows.device) if want_u8 else None
+    N.check(N.lib().adm_window_crossfade(N.ptr(windows), N.ptr(out), N.ptr(u8), BW // nW, Cc, H, int(total_w), W, int(stride),
+                                         int(bool(wrap)), N.stream_for(windows)))
+    return (out, u8) if want_u8 else out
+
+
 def _sched_args(x, eps, coef_table, step, step_dev, prediction, uncond, guidance_scale, out=None, u8_out=None, noise=None, mask=None,
                 mask_start=0, mask_end=0, guidance_rescale=None, rescale_out=None):
     """The `adm_sched_step_args` (include/adm.h) of a plain step on x, eps: (B,C,H,W); the callers add their mode's fields.

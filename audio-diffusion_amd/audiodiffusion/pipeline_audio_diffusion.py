@@ -213,9 +213,9 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             if given:
                 raise ValueError(f"`{name}` cannot be combined with `frames`: windowed sampling starts from noise and has no mask "
                                  f"(the mask's layout assumes the model's width)")
-        if self.vqvae is not None:
-            raise NotImplementedError("`frames` with a `vqvae` is not implemented: the decoder's mid-block attention would see another "
-                                      "sequence length than the one it was trained on")
+        if self.vqvae is not None and not hasattr(self.vqvae, "decode_tiled"):
+            raise NotImplementedError("`frames` with a `vqvae` that has no `decode_tiled` is not implemented: the decoder's mid-block "
+                                      "attention would see another sequence length than the one it was trained on")
         W = self.unet._hw()[1]
         stride = W // 2 if window_stride is None else window_stride
         nW = ops.window_count(frames, W, stride, circular, names=("frames", "window_stride", "circular"))
@@ -270,6 +270,21 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             rows.append((1.0, 0.0))
         assert len(rows) == n
         return rows
+
+    def _vae_factor(self):
+        """Image pixels per latent cell along an axis (1 without a `vqvae`): `frames` counts cells of the tensor being denoised."""
+        return 1 if self.vqvae is None else 2 ** (len(self.vqvae.config.block_out_channels) - 1)
+
+    def _encode_known(self, input_images, window, generator):
+        """The audio input's image (1, H, W) in [-1, 1] -> the scaled latent (Cz, h, w) of a `vqvae` pipeline. With windowed sampling the
+        image is wide and goes through the tiled encoder at the sampler's own placement, in pixels."""
+        x = torch.unsqueeze(input_images, 0)
+        if window is None:
+            dist = self.vqvae.encode(x).latent_dist
+        else:
+            f = self._vae_factor()
+            dist = self.vqvae.encode_tiled(x, f * self.unet._hw()[1], f * window[1], window[2]).latent_dist
+        return 0.18215 * dist.sample(generator=generator)[0]
 
     def _wide_mel(self, frames):
         """A Mel of the pipeline's Mel config with x_res = frames (the codec requires the image width to equal x_res): a separate object,
@@ -481,10 +496,15 @@ class AudioDiffusionPipeline(DiffusionPipeline):
           * `noise`, if given, is (batch_size, C, H, frames); device noise draws the initial latent at that shape. Everything per sample
             (thresholding, guidance rescale, the device-noise counter) is per wide sample. `encoding` rows serve all windows of a sample.
           * `window_stride` or `circular` without `frames`, and `audio_file`, `raw_audio`, `mask_start_secs` or `mask_end_secs` with it:
-            ValueError. With a `vqvae`: NotImplementedError.
-          * images come back `frames` wide; audio is decoded through a separate Mel of this pipeline's Mel config with x_res = frames
-            and is hop_length * (frames - 1) samples long. The Griffin-Lim phase of a circular image is NOT made circular: the seamless
-            object is the spectrogram.
+            ValueError.
+          * with a `vqvae` (latent audio diffusion) `frames`, `window_stride` and `noise` are in units of the tensor being denoised,
+            latent cells of f = 2^(VAE blocks - 1) pixels, as `keep_mask` is. The wide latent is decoded by `vqvae.decode_tiled` at the
+            sampler's own placement (windows of the UNet's width, `window_stride`, `circular`): all windows as one decoder batch, joined
+            in pixel space by a cross-fade whose weights fall off towards each window's edges (include/adm.h "Tiled codec"), so the
+            decoder's global attention never sees a wide latent. A `vqvae` object without `decode_tiled`: NotImplementedError.
+          * images come back `frames` wide (f*frames with a `vqvae`); audio is decoded through a separate Mel of this pipeline's Mel
+            config with x_res = that width and is hop_length * (width - 1) samples long. The Griffin-Lim phase of a circular image is NOT
+            made circular: the seamless object is the spectrogram.
 
         Region in-painting, off by default: `keep_mask`, `known_level`, `known` (include/adm.h "Region in-painting"). `keep_mask` is a
         bool or 0/1 tensor or array (H, W), (1, H, W) or (B, H, W) at the resolution of the tensor being denoised (image pixels; latent
@@ -492,7 +512,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         in the middle of a clip, a frequency band, single pixels; any channel count (the mask is broadcast over the channels).
           * `keep_mask=None` is the path without it, exactly.
           * the known image comes from `audio_file` / `raw_audio` (+ `slice`), converted as for `mask_start_secs` (with a `vqvae`:
-            encoded and scaled by 0.18215; with `frames`: through a Mel of this pipeline's config with x_res = frames), or from `known`,
+            encoded and scaled by 0.18215; with `frames`: through a Mel of this pipeline's config with x_res = the image width, and
+            with both through `vqvae.encode_tiled` at the sampler's placement, ONE posterior draw at the wide shape), or from `known`,
             a float tensor (1 or B, C, H, W) already in model space ([-1, 1] images, or scaled latents). One of them is needed, not both.
           * after every step the kept elements are overwritten with ka*known + kb*noise INSIDE the step kernel: no (B, steps, H, W) mask
             tensor is built, nothing is staged per step, and the run is the same native call(s) as without the mask.
@@ -505,7 +526,7 @@ class AudioDiffusionPipeline(DiffusionPipeline):
           * `start_step > 0`: every sample (not only [0, 0] as with `mask_start_secs`) starts from add_noise(known, noise,
             timesteps[start_step - 1]).
           * with `mask_start_secs` / `mask_end_secs`, without a source, with a mask or a `known` of another shape, or with another
-            `known_level`: ValueError naming the keyword. `frames` + `vqvae` stays NotImplementedError."""
+            `known_level`: ValueError naming the keyword. `frames` with a `vqvae` that cannot decode tiles stays NotImplementedError."""
         ops.guidance_rescale_on(guidance_rescale, self._guided(guidance_scale, negative_encoding, encoding))   # the ValueErrors, before any work
         self._device_noise(device_noise_seed, generator=generator, step_generator=step_generator, step_noise=step_noise)
         # For backwards compatibility
@@ -543,15 +564,14 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             # it, and no (B, steps, H, W) mask: the step kernel forms add_noise(known, noise, level) where keep_mask says so
             known = kept[1]
             if known is None:
-                mel = self.mel if window is None else self._wide_mel(window[0])
+                mel = self.mel if window is None else self._wide_mel(self._vae_factor() * window[0])
                 mel.load_audio(audio_file, raw_audio)
                 input_image = mel.audio_slice_to_image(slice)
                 input_image = np.frombuffer(input_image.tobytes(), dtype="uint8").reshape((input_image.height, input_image.width))
                 input_image = (input_image / 255) * 2 - 1
                 input_images = torch.tensor(input_image[np.newaxis, :, :], dtype=torch.float).to(self.device)
                 if self.vqvae is not None:
-                    input_images = self.vqvae.encode(torch.unsqueeze(input_images, 0)).latent_dist.sample(generator=generator)[0]
-                    input_images = 0.18215 * input_images
+                    input_images = self._encode_known(input_images, window, generator)
                 known = input_images[None].contiguous()
                 if tuple(known.shape[1:]) != shape[1:]:
                     raise ValueError(f"the audio input gives a known image of shape {tuple(known.shape[1:])}, the sample is {shape[1:]}: "
@@ -594,7 +614,12 @@ class AudioDiffusionPipeline(DiffusionPipeline):
                                    circular=window is not None and window[2], keep_mask=None if kept is None else kept[0],
                                    known=known if kept is not None else None, known_noise=known_noise, known_level=known_level)
 
-        if self.vqvae is not None:
+        if self.vqvae is not None and window is not None:
+            # the wide latent never reaches the decoder as it is: windows of the UNet's width at the sampler's own placement, decoded as
+            # one batch and cross-faded in pixel space (include/adm.h "Tiled codec"); the bytes come from the cross-fade kernel
+            tiled = self.vqvae.decode_tiled(images, self.unet._hw()[1], window[1], window[2], _in_scale=1 / 0.18215, want_u8=True)
+            images, u8 = tiled["sample"], tiled["u8"].permute(0, 2, 3, 1).contiguous()
+        elif self.vqvae is not None:
             # 0.18215 was scaling factor used in training to ensure unit variance (pipeline:187-190); the 1/0.18215
             # multiply is folded into the decoder launch
             images = self.vqvae.decode(images, _in_scale=1 / 0.18215)["sample"]
@@ -614,7 +639,8 @@ class AudioDiffusionPipeline(DiffusionPipeline):
         # through the Mel kernels in one launch sequence
         audios = []
         if audio:
-            mel = self.mel if window is None else self._wide_mel(window[0])   # (the codec requires the image width to equal x_res)
+            # (the codec requires the image width to equal x_res; with a `vqvae` the image is f times as wide as the latent)
+            mel = self.mel if window is None else self._wide_mel(self._vae_factor() * window[0])
             audios = list(mel.images_to_audios(images, init_phase=init_phase))
         if return_float:
             return images, final_float

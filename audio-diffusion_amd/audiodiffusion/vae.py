@@ -107,6 +107,33 @@ class DiagonalGaussianDistribution:
         return self._vae._encode(self._x, None, 1.0)
 
 
+class TiledGaussianDistribution:
+    """`latent_dist` of `vqvae.encode_tiled(...)`: the cross-faded moments (B, 2*Cz, h, Wt) stay on the device; `.sample()` launches the
+    encoder's own sampling tail on them (`adm_vae_sample_moments`), ONE noise draw at the wide latent shape."""
+
+    def __init__(self, vae, moments):
+        self._vae, self.moments = vae, moments
+
+    def _sample(self, noise):
+        B, C2, h, w = self.moments.shape
+        z = torch.empty((B, C2 // 2, h, w), dtype=torch.float32, device=self.moments.device)
+        N.check(N.lib().adm_vae_sample_moments(N.ptr(self.moments), N.ptr(noise), C.c_float(1.0), N.ptr(z), B, C2 // 2, h * w,
+                                               N.stream_for(self.moments)))
+        return z
+
+    def sample(self, generator=None, noise=None):
+        B, C2, h, w = self.moments.shape
+        shape = (B, C2 // 2, h, w)
+        if noise is None:
+            noise = randn_tensor(shape, generator, self.moments.device, torch.float32)
+        if tuple(noise.shape) != shape:
+            raise ValueError(f"noise shape {tuple(noise.shape)} is not the wide latent's {shape}")
+        return self._sample(noise.to(self.moments.device, torch.float32).contiguous())
+
+    def mode(self):
+        return self._sample(None)
+
+
 class EncoderOutput:
     def __init__(self, dist):
         self.latent_dist = dist
@@ -243,6 +270,51 @@ class AutoencoderKL:
         out = torch.empty((B, self.config.out_channels) + hw, dtype=torch.float32, device=z.device)
         N.check(N.lib().adm_vae_decode(h, N.ptr(z), C.c_float(_in_scale), N.ptr(out), B, N.stream_for(z)))
         return DecoderOutput(sample=out)
+
+    # ---- tiled codec (include/adm.h "Tiled codec") ---------------------------------------------------------------
+    def _factor(self):
+        return 2 ** (len(self.config.block_out_channels) - 1)
+
+    def decode_tiled(self, z, tile_w, stride, circular=False, _in_scale=1.0, want_u8=False):
+        """`decode` of a latent (B, Cz, h, Wt) wider than the width the VAE was trained at: windows of latent width `tile_w`, `stride`
+        apart (the placement rules of windowed sampling, `circular` on a circle), ALL windows of all samples decoded as one batch — the
+        mid-block attention, which is global, sees the sequence length of a `tile_w`-wide latent only — and joined in pixel space by the
+        cross-fade of `ops.window_crossfade`, whose weights fall off towards a window's own edges. Exactly `ops.window_gather` -> `decode`
+        -> `ops.window_crossfade`; with Wt == tile_w it is `decode(z)`. want_u8: the result also carries `u8`, the bytes
+        `ops.dequant_u8(sample)` gives, written by the cross-fade kernel."""
+        from . import ops
+        assert z.dim() == 4 and z.dtype == torch.float32
+        f = self._factor()
+        Wt = z.shape[3]
+        ops.window_count(Wt, tile_w, stride, circular, names=("the latent's width", "stride", "circular"))
+        windows = ops.window_gather(z.contiguous(), tile_w, stride, circular)
+        pixels = self.decode(windows, _in_scale=_in_scale)["sample"]
+        out = ops.window_crossfade(pixels, f * Wt, f * int(stride), circular, want_u8=want_u8)
+        return DecoderOutput(sample=out[0], u8=out[1]) if want_u8 else DecoderOutput(sample=out)
+
+    def encode_tiled(self, x, tile_w, stride, circular=False):
+        """`encode` of an image (B, Cin, H, Wt) wider than the VAE was trained at; `tile_w` and `stride` in PIXELS, multiples of 4*f so
+        that the latent placement (both divided by f = 2^(blocks - 1)) is admissible. All pixel windows are encoded as one batch; their
+        moments (means and log-variances, 2*Cz channels) are cross-faded to the wide latent shape BEFORE the sampling, so ONE noise draw
+        at the wide shape serves. -> EncoderOutput whose `latent_dist.sample(generator=, noise=)` / `.mode()` give (B, Cz, h, Wt / f)."""
+        from . import ops
+        assert x.dim() == 4 and x.dtype == torch.float32
+        f = self._factor()
+        for name, v in (("tile_w", tile_w), ("stride", stride)):
+            if int(v) <= 0 or int(v) % (4 * f):
+                raise ValueError(f"{name}={v} must be a positive multiple of {4 * f} pixels (4 latent cells of {f} pixels)")
+        Wt = x.shape[3]
+        ops.window_count(Wt, tile_w, stride, circular, names=("the image's width", "stride", "circular"))
+        windows = ops.window_gather(x.contiguous(), tile_w, stride, circular)
+        h = self._ensure_handle(windows.shape[2:])
+        BW = windows.shape[0]
+        lh, lw = self.latent_size(windows.shape[2:])
+        Cz = self.config.latent_channels
+        z = torch.empty((BW, Cz, lh, lw), dtype=torch.float32, device=x.device)          # (the windows' own modes: not used)
+        moments = torch.empty((BW, 2 * Cz, lh, lw), dtype=torch.float32, device=x.device)
+        N.check(N.lib().adm_vae_encode(h, N.ptr(windows), None, C.c_float(1.0), N.ptr(z), N.ptr(moments), BW, N.stream_for(x)))
+        wide = ops.window_crossfade(moments, Wt // f, int(stride) // f, circular)
+        return EncoderOutput(TiledGaussianDistribution(self, wide))
 
     # ---- diffusers on-disk layout ------------------------------------------------------------------------------
     @classmethod

@@ -53,6 +53,8 @@ int launch_dequant(const float* x, uint8_t* out, long n, hipStream_t st);
 int window_count(const char* who, const char* pre, int total_w, int W, int stride, int wrap, int* nW);
 int launch_window_gather(const float* x, float* windows, int B, int C, int H, int total_w, int W, int stride, int wrap, hipStream_t st);
 int launch_window_blend(const float* windows, float* out, int B, int C, int H, int total_w, int W, int stride, int wrap, hipStream_t st);
+int launch_window_crossfade(const float* windows, float* out, uint8_t* u8_out, int B, int C, int H, int total_w, int W, int stride, int wrap,
+                            hipStream_t st);
 
 // k_groupnorm.hip
 int launch_groupnorm_finalize(const double* st1, int C1, int tiles1, const double* st2, int C2, int tiles2, int N, int HW,

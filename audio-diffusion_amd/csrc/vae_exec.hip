@@ -220,6 +220,12 @@ int adm_vae_encode(adm_vae_t* h, const float* x, const float* noise, float out_s
   return launch_gaussian_sample(mom, noise, z_out, B, Cz, hw, out_scale, st);
 }
 
+int adm_vae_sample_moments(const float* moments, const float* noise, float out_scale, float* z_out, int B, int Cz, long n, void* stream) {
+  ADM_REQUIRE(moments && z_out, "vae_sample_moments: null argument");
+  ADM_REQUIRE(B > 0 && Cz > 0 && n > 0, "vae_sample_moments: B, Cz and n must be positive");
+  return launch_gaussian_sample(moments, noise, z_out, B, Cz, n, out_scale, (hipStream_t)stream);
+}
+
 int adm_vae_decode(adm_vae_t* h, const float* z, float in_scale, float* out, int B, void* stream) {
   ADM_REQUIRE(h && z && out, "vae_decode: null argument");
   hipStream_t st = (hipStream_t)stream;

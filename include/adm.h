@@ -412,6 +412,30 @@ typedef struct adm_unipc_coef {
 int adm_window_gather(const float* x, float* windows, int B, int C, int H, int total_w, int W, int stride, int wrap, void* stream);
 int adm_window_blend(const float* windows, float* out, int B, int C, int H, int total_w, int W, int stride, int wrap, void* stream);
 
+/* Tiled codec (adm_version() >= 121): the cross-fade that joins the windows of a tensor that went through a model window by window AFTER
+ * sampling (AutoencoderKL.decode_tiled / encode_tiled: the VAE's mid-block attention is global, so it only ever sees windows of the width
+ * it was trained at). THE definition. The blend's plain mean is the right fusion of model outputs inside a step; a decoder's image is
+ * distorted towards ITS OWN edges by the zero padding of its stacked 3x3 convolutions, so here a window's weight falls off towards every
+ * edge that has a neighbour. Layout, placement rules and refusals are those of "Windowed sampling" above: windows (B*nW,C,H,W),
+ * sample-major, as adm_window_gather writes them; out (B,C,H,Wt).
+ * Weights: r = W - s, the overlap of neighbouring windows. Window w, local column j, integer weight m_w(j):
+ *   r == 0: m = 1.   Otherwise m = min(a, b) with
+ *   a = min(2j + 1, 2r)           if the window has a left neighbour,  else 2r
+ *   b = min(2(W - 1 - j) + 1, 2r) if it has a right neighbour,         else 2r
+ *   open: window 0 has no left neighbour and window nW-1 no right one. circular: every window has both, except that nW == 1 has neither.
+ *   m is an integer in [1, 2r], exact in fp32. With s == W/2 the weights over a column sum to the constant 2r (the linear cross-fade of
+ *   two windows); with a cover above 2 it is not constant in general (the open placement Wt = 24, W = 16, s = 4 gives 24..31), hence the
+ *   normalisation.
+ * Output: out[b,c,y,col] = (float(m_w0)*o_w0 + float(m_w1)*o_w1 + ...) / float(m_w0 + m_w1 + ...) over the windows that cover col, in the
+ *   blend's order (ascending index: the windows that reach col without wrapping, then the wrapping ones); the sum starts from the first
+ *   product; every product and every addition is rounded to fp32 on its own (no contraction); the weights are summed as integers; one
+ *   IEEE division. A column covered by ONE window is that window's value, copied ((m*o)/m is not o in fp32). No atomics, no table: the
+ *   result depends on neither the launch geometry nor a replay.
+ * u8_out: NULL, or (B,C,H,Wt) bytes: what adm_dequant_u8 gives for `out`, element for element, written from the value just computed.
+ * Traffic: 4 B read per window element + 4 B (+ 1 B with u8_out) written per wide element. */
+int adm_window_crossfade(const float* windows, float* out, uint8_t* u8_out /* may be NULL */, int B, int C, int H, int total_w, int W,
+                         int stride, int wrap, void* stream);
+
 /* scheduler.add_noise (rows S4,P3,T3): out[b][n][p] = sa[b*cb+n*cn]*x0[b*x0_bstride+p] + sb[..]*noise[b*P+p];
  * sa/sb are device arrays (sqrt(acp[t]), sqrt(1-acp[t])). */
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb,
@@ -788,6 +812,9 @@ int adm_vae_encode(adm_vae_t* h, const float* x, const float* noise, float out_s
                    int B, void* stream);
 /* out (B,Cout,H,W) = decoder(post_quant_conv(in_scale * z)); in_scale carries the reference's 1/0.18215. */
 int adm_vae_decode(adm_vae_t* h, const float* z, float in_scale, float* out, int B, void* stream);
+/* The tail of adm_vae_encode as a launch of its own (adm_version() >= 121; the same kernel, not a second formula): z_out (B,Cz,n) from
+ * moments (B,2*Cz,n) = [mean | logvar] that the caller holds, e.g. the cross-faded moments of a tiled encode; noise (B,Cz,n) or NULL (mode). */
+int adm_vae_sample_moments(const float* moments, const float* noise, float out_scale, float* z_out, int B, int Cz, long n, void* stream);
 /* The plan report of adm_unet_plan_ops for the encoder (which = 0, quant_conv included) or the decoder (1, post_quant_conv included). */
 int adm_vae_plan_ops(adm_vae_t* h, int which, int B, adm_plan_op* recs, int cap, int* n_out);
 
