@@ -14,9 +14,33 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "net_exec.h"
+
+namespace adm {
+// One step of a loop, described: everything its launches depend on that can differ between two loop calls on the same plan. enqueue_step
+// launches from this and sees nothing else of the call, and run_loop replays the stored graph exactly when two of these are the same bytes;
+// so what reaches a kernel argument is in the comparison by construction. describe_step fills it, a feature that is off as zeros. Per-plan
+// buffers are not here: when one moves, free_plan forgets the stored step. Floats are held as their bits and there is no padding.
+struct StepDesc {
+  float* x; const float* step_noise; const float* mask; uint8_t* u8_out;   // the caller's tensors
+  const float* encoding_uncond;                                             // guided
+  const float *known, *known_noise; const uint8_t* keep;                    // in-painting
+  // the handle's: the coefficient table and, where the step reads them, the multistep / UniPC / known-region tables and the noise-stream
+  // block (a table that is set selects its step: unipc the UniPC step, noise_blk the noise drawn on the device); the encoding
+  const adm_sched_coef* coef; const float* khist; const adm_unipc_coef* unipc; const float* known_tab; const uint32_t* noise_blk;
+  const float* ctx;
+  hipStream_t stream;
+  int32_t B, n_steps, mask_start, mask_end, mode, prediction, ctx_S;
+  int32_t lo, hi; uint32_t w, max_value;                 // SCHED_THRESH
+  uint32_t guidance_scale, guidance_rescale;             // guided
+  int32_t window_total_w, window_stride, window_wrap;    // windowed
+  int32_t known_batched, keep_batched;                   // in-painting
+};
+static_assert(std::has_unique_object_representations_v<StepDesc>, "StepDesc is compared as bytes: no padding, no float members");
+}  // namespace adm
 
 extern "C" int adm_mse_loss(const float* pred, const float* target, long n, float* loss_out, float* grad_out,
                             double* scratch, void* stream);
@@ -39,25 +63,25 @@ struct adm_unet {
   float* hist_buf = nullptr;     // x0 of the previous step (multistep scheduler loop); same size as eps_buf
   float* scale_buf = nullptr;    // per-sample dynamic threshold of the thresholded loop (B floats)
   float* rescale_buf = nullptr;  // per-sample guidance-rescale factor r_b of the rescaled guided loop (B floats)
-  float* eps_uncond_buf = nullptr;   // the unconditional forward's output of a guided loop; same size as eps_buf, allocated with the
-                                     // plan by the first guided loop at this batch size (free_plan releases it with the other extras)
+  // Per-plan buffers allocated by the first loop that needs them at this batch size (run_loop) and released with the plan's other extras;
+  // free_plan resets the struct by value, so a buffer added here cannot be left dangling.
+  struct LazyBufs {
+    float* eps_uncond = nullptr;   // the unconditional forward's output of a guided loop; same size as eps_buf
+    float* unipc = nullptr;        // the UniPC loop's state: the two history slots, then `last` (three times eps_buf's size)
+    // the windowed loop (include/adm.h "Windowed sampling"): the gathered windows (the forwards' input) and the blended model outputs of
+    // the wide shape (the step's eps / eps_uncond). Each of eps_buf's size — nW*W >= Wt, so a wide tensor fits where the windows do
+    float *win = nullptr, *wide_eps = nullptr, *wide_uncond = nullptr;
+  } lazy;
+  // per-step device tables beside coef_dev, each grown by upload_rows: the multistep history coefficient, the UniPC loop's adm_unipc_coef,
+  // the (ka, kb) of the known-region overwrite (include/adm.h "Region in-painting")
   adm_sched_coef* coef_dev = nullptr;
-  int coef_cap = 0;
-  float* khist_dev = nullptr;    // per-step history coefficient of the multistep loop, beside coef_dev
-  int khist_cap = 0;
-  float* unipc_buf = nullptr;    // the UniPC loop's state: the two history slots, then `last` (three times eps_buf's size); allocated with
-                                 // the plan by the first UniPC loop at this batch size, as eps_uncond_buf is
-  adm_unipc_coef* unipc_dev = nullptr;   // per-step adm_unipc_coef of the UniPC loop, beside coef_dev
-  int unipc_cap = 0;
-  float* known_dev = nullptr;    // per-step (ka, kb) of the known-region overwrite (include/adm.h "Region in-painting"), beside coef_dev
-  int known_cap = 0;
-  // the windowed loop (include/adm.h "Windowed sampling"): the gathered windows (the forwards' input) and the blended model outputs of
-  // the wide shape (the step's eps / eps_uncond). Each of eps_buf's size — nW*W >= Wt, so a wide tensor fits where the windows do —
-  // allocated with the plan by the first windowed loop at this batch size, as eps_uncond_buf is
-  float *win_buf = nullptr, *wide_eps_buf = nullptr, *wide_uncond_buf = nullptr;
+  float* khist_dev = nullptr;
+  adm_unipc_coef* unipc_dev = nullptr;
+  float* known_dev = nullptr;
+  int coef_cap = 0, khist_cap = 0, unipc_cap = 0, known_cap = 0;
   int* step_dev = nullptr;
   // the noise-stream block of adm_sample_loop_philox: {seed_lo, seed_hi, row_offset, stream id}. Allocated once and never moved (its address
-  // is in the captured graph's key); rewritten from noise_blk_host by a stream-ordered copy before every run.
+  // is part of the captured step's description); rewritten from noise_blk_host by a stream-ordered copy before every run.
   uint32_t* noise_blk_dev = nullptr;
   uint32_t noise_blk_host[4] = {0, 0, 0, 0};
   // training
@@ -69,11 +93,11 @@ struct adm_unet {
   long params_numel = 0;
   float *dtemb_all = nullptr, *demb = nullptr, *dz = nullptr, *save_sinus = nullptr, *save_z = nullptr;
   double* scratch_d = nullptr;
+  adm::StepDesc captured{};   // the step the last use_graph loop captured (all zeros: none; a step has an x); the emulator keeps it too
+  int captures = 0;           // adm_unet_loop_captures
 #if !defined(ADM_EMU)
   hipStream_t own_stream = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  hipStream_t gstream = nullptr;     // the stream gexec was captured on and is replayed on
-  std::vector<uint64_t> gkey;
+  hipGraphExec_t gexec = nullptr;    // `captured` as an executable graph, replayed on captured.stream
 #endif
 };
 
@@ -274,18 +298,16 @@ static void free_plan(adm_unet* h) {
   for (void* p : h->extra) dfree(p);
   h->extra.clear();
   h->planned_B = 0;
-  h->eps_uncond_buf = nullptr;
-  h->unipc_buf = nullptr;
-  h->win_buf = h->wide_eps_buf = h->wide_uncond_buf = nullptr;
+  h->lazy = {};
   h->warm_B = 0;       // the next capture is preceded by an uncaptured forward again (another kernel's one-time set-up)
 #if !defined(ADM_EMU)
   if (h->gexec) {                     // (a replay may still be in flight: drain the stream it ran on before the executable graph goes)
-    (void)stream_sync(h->gstream);
+    (void)stream_sync(h->captured.stream);
     (void)hipGraphExecDestroy(h->gexec);
     h->gexec = nullptr;
   }
-  h->gkey.clear();
 #endif
+  h->captured = {};
 }
 
 static int extra_alloc(adm_unet* h, void** p, size_t bytes) {
@@ -293,6 +315,9 @@ static int extra_alloc(adm_unet* h, void** p, size_t bytes) {
   h->extra.push_back(*p);
   return 0;
 }
+
+// A member of adm_unet::LazyBufs: allocated with the plan by the first loop that needs it.
+static int ensure(adm_unet* h, float** p, size_t elems) { return *p ? 0 : extra_alloc(h, (void**)p, sizeof(float) * elems); }
 
 static int plan(adm_unet* h, int B) {
   // (re-planned as well when adm_set_option has moved since: a layer may have changed kernel, and the partial-sum buffers of the
@@ -339,38 +364,15 @@ static int run_forward(adm_unet* h, const float* x, float* out, int B, const adm
   return h->net.run(x, out, B, h->temb_all, h->temb_rows, st, tm);
 }
 
-static int ensure_coef(adm_unet* h, const adm_sched_coef* coef_host, int n, hipStream_t st) {
-  if (h->coef_cap < n) {
-    ADM_TRY(dalloc(h, (void**)&h->coef_dev, sizeof(adm_sched_coef) * (size_t)n));
-    h->coef_cap = n;
+// One of the handle's per-step device tables: grown to n rows when it is smaller (it then moves, and a captured step that read it is
+// captured again), then filled from the host rows in stream order.
+template <class T>
+static int upload_rows(adm_unet* h, T** dev, int* cap, const T* host, size_t row_bytes, int n, hipStream_t st) {
+  if (*cap < n) {
+    ADM_TRY(dalloc(h, (void**)dev, row_bytes * (size_t)n));
+    *cap = n;
   }
-  ADM_TRY(copy_h2d(h->coef_dev, coef_host, sizeof(adm_sched_coef) * (size_t)n, st));
-  ADM_TRY(dmemset(h->step_dev, 0, sizeof(int), st));
-  return 0;
-}
-
-static int ensure_khist(adm_unet* h, const float* k_hist_host, int n, hipStream_t st) {
-  if (h->khist_cap < n) {
-    ADM_TRY(dalloc(h, (void**)&h->khist_dev, sizeof(float) * (size_t)n));
-    h->khist_cap = n;
-  }
-  return copy_h2d(h->khist_dev, k_hist_host, sizeof(float) * (size_t)n, st);
-}
-
-static int ensure_unipc(adm_unet* h, const adm_unipc_coef* unipc_host, int n, hipStream_t st) {
-  if (h->unipc_cap < n) {
-    ADM_TRY(dalloc(h, (void**)&h->unipc_dev, sizeof(adm_unipc_coef) * (size_t)n));
-    h->unipc_cap = n;
-  }
-  return copy_h2d(h->unipc_dev, unipc_host, sizeof(adm_unipc_coef) * (size_t)n, st);
-}
-
-static int ensure_known(adm_unet* h, const float* known_coef_host, int n, hipStream_t st) {
-  if (h->known_cap < n) {
-    ADM_TRY(dalloc(h, (void**)&h->known_dev, sizeof(float) * 2 * (size_t)n));
-    h->known_cap = n;
-  }
-  return copy_h2d(h->known_dev, known_coef_host, sizeof(float) * 2 * (size_t)n, st);
+  return copy_h2d(*dev, host, row_bytes * (size_t)n, st);
 }
 
 // adm_sample_loop_args::mode inside this file: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
@@ -379,7 +381,7 @@ enum { LOOP_ENCODE = -1 };
 using LoopArgs = adm_sample_loop_args;
 // LoopArgs::encoding_uncond and guidance_scale: classifier-free guidance (the unconditional encoding, device, of the shape of the handle's).
 // LoopArgs::seed and row_offset (noise_source 1, "adm noise stream 1": the seed and the global row of x[0]) reach the kernel through the
-// handle's device block, never as kernel arguments: neither is part of the captured graph's key.
+// handle's device block, never as kernel arguments: neither is in the StepDesc.
 
 // The noise-stream block, written in stream order before the first step and outside the captured step.
 static int ensure_noise_block(adm_unet* h, const LoopArgs& a, hipStream_t st) {
@@ -391,74 +393,103 @@ static int ensure_noise_block(adm_unet* h, const LoopArgs& a, hipStream_t st) {
 
 // The windowed loop (LoopArgs::window_total_w != 0; include/adm.h "Windowed sampling"): windows per wide sample. adm_sample_loop_ex has
 // checked the placement, so the count is the definition's quotient.
-static int loop_windows(const adm_unet* h, const LoopArgs& a) {
+template <class A>   // LoopArgs (before there is a plan) or StepDesc
+static int loop_windows(const adm_unet* h, const A& a) {
   if (a.window_total_w == 0) return 1;
   return a.window_wrap ? a.window_total_w / a.window_stride : (a.window_total_w - h->cfg.sample_w) / a.window_stride + 1;
 }
 
-static int gather_windows(adm_unet* h, const LoopArgs& a, hipStream_t st) {
-  const adm_unet_config& c = h->cfg;
-  return launch_window_gather(a.x, h->win_buf, a.B, c.in_channels, c.sample_h, a.window_total_w, c.sample_w, a.window_stride,
-                              a.window_wrap, st);
+static uint32_t f32_bits(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
+static float bits_f32(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
+
+// The step of loop `a` run on stream `run`, after plan(), the lazy buffers and the table uploads (any of which may move what this reads
+// from the handle). Normalised: the fields of a feature that is off stay zero, whatever the caller left in them, because the launchers do
+// not read them then (launch_sched_threshold is reached in SCHED_THRESH only; guidance and the rescale need eps_uncond; the window fields
+// are read under window_total_w != 0 and the known-region fields under keep != NULL; k_hist_table is read by the multistep kernels only).
+static StepDesc describe_step(const adm_unet* h, const LoopArgs& a, hipStream_t run) {
+  StepDesc d{};
+  d.x = a.x; d.step_noise = a.step_noise; d.mask = a.mask; d.u8_out = a.u8_out;
+  d.B = a.B; d.n_steps = a.n_steps; d.mask_start = a.mask_start; d.mask_end = a.mask_end; d.mode = a.mode; d.prediction = a.prediction;
+  d.coef = h->coef_dev; d.ctx = h->net.ctx; d.ctx_S = h->net.ctx_S; d.stream = run;
+  if (a.mode == SCHED_THRESH) { d.lo = a.lo; d.hi = a.hi; d.w = f32_bits(a.w); d.max_value = f32_bits(a.max_value); }
+  if (a.mode == SCHED_MULTISTEP) d.khist = h->khist_dev;
+  if (a.unipc_host != nullptr) d.unipc = h->unipc_dev;
+  if (a.noise_source == 1) d.noise_blk = h->noise_blk_dev;
+  if (a.encoding_uncond != nullptr) {
+    d.encoding_uncond = a.encoding_uncond; d.guidance_scale = f32_bits(a.guidance_scale); d.guidance_rescale = f32_bits(a.guidance_rescale);
+  }
+  if (a.window_total_w != 0) { d.window_total_w = a.window_total_w; d.window_stride = a.window_stride; d.window_wrap = a.window_wrap; }
+  if (a.keep != nullptr) {
+    d.known = a.known; d.known_noise = a.known_noise; d.keep = a.keep; d.known_tab = h->known_dev;
+    d.known_batched = a.known_batched != 0; d.keep_batched = a.keep_batched != 0;
+  }
+  return d;
 }
 
-// One denoising step; every step-dependent scalar is read on the device through *step_dev.
-static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st) {
+static int gather_windows(adm_unet* h, const StepDesc& d) {
   const adm_unet_config& c = h->cfg;
-  const adm_sched_coef* table = h->coef_dev;
+  return launch_window_gather(d.x, h->lazy.win, d.B, c.in_channels, c.sample_h, d.window_total_w, c.sample_w, d.window_stride,
+                              d.window_wrap, d.stream);
+}
+
+// One denoising step on d.stream; every step-dependent scalar is read on the device through *step_dev.
+static int enqueue_step(adm_unet* h, const StepDesc& d, int step) {
+  const adm_unet_config& c = h->cfg;
+  const hipStream_t st = d.stream;
+  const bool guided = d.encoding_uncond != nullptr;
   // windowed: gather, the forward(s) on the windows as ONE batch of B*nW, one blend per model output, then the step on the wide tensors
-  const bool windowed = a.window_total_w != 0;
-  const int FB = a.B * loop_windows(h, a);                      // the forwards' batch
-  const int Wx = windowed ? a.window_total_w : c.sample_w;      // the width of x, and of everything the step touches
-  const float* fx = a.x;
+  const bool windowed = d.window_total_w != 0;
+  const int FB = d.B * loop_windows(h, d);                      // the forwards' batch
+  const int Wx = windowed ? d.window_total_w : c.sample_w;      // the width of x, and of everything the step touches
+  const float* fx = d.x;
   if (windowed) {
-    ADM_TRY(gather_windows(h, a, st));
-    fx = h->win_buf;
+    ADM_TRY(gather_windows(h, d));
+    fx = h->lazy.win;
   }
-  ADM_TRY(run_forward(h, fx, h->eps_buf, FB, table, st));
-  if (a.encoding_uncond != nullptr) {
+  ADM_TRY(run_forward(h, fx, h->eps_buf, FB, d.coef, st));
+  if (guided) {
     // The unconditional branch: a second forward of batch B on the SAME plan (its side-stream hoists included), with the encoding pointer
     // swapped. Nothing derived from the encoding outlives a forward (the cross-attention kernel projects K and V from net.ctx inside every
     // launch), so the swap is all it takes; both forwards run in stream order, the second after the first has joined its side launches.
     const float* ctx_cond = h->net.ctx;
-    h->net.ctx = a.encoding_uncond;
-    const int rc = run_forward(h, fx, h->eps_uncond_buf, FB, table, st);
+    h->net.ctx = d.encoding_uncond;
+    const int rc = run_forward(h, fx, h->lazy.eps_uncond, FB, d.coef, st);
     h->net.ctx = ctx_cond;
     ADM_TRY(rc);
   }
-  const float *eps = h->eps_buf, *eps_uncond = h->eps_uncond_buf;
+  const float *eps = h->eps_buf, *eps_uncond = h->lazy.eps_uncond;
   if (windowed) {
-    ADM_TRY(launch_window_blend(eps, h->wide_eps_buf, a.B, c.out_channels, c.sample_h, Wx, c.sample_w, a.window_stride, a.window_wrap, st));
-    eps = h->wide_eps_buf;
-    if (a.encoding_uncond != nullptr) {
-      ADM_TRY(launch_window_blend(eps_uncond, h->wide_uncond_buf, a.B, c.out_channels, c.sample_h, Wx, c.sample_w, a.window_stride,
-                                  a.window_wrap, st));
-      eps_uncond = h->wide_uncond_buf;
+    ADM_TRY(launch_window_blend(eps, h->lazy.wide_eps, d.B, c.out_channels, c.sample_h, Wx, c.sample_w, d.window_stride, d.window_wrap, st));
+    eps = h->lazy.wide_eps;
+    if (guided) {
+      ADM_TRY(launch_window_blend(eps_uncond, h->lazy.wide_uncond, d.B, c.out_channels, c.sample_h, Wx, c.sample_w, d.window_stride,
+                                  d.window_wrap, st));
+      eps_uncond = h->lazy.wide_uncond;
     }
   }
-  const long n = (long)a.B * c.in_channels * c.sample_h * Wx;
-  if (a.mode == LOOP_ENCODE) {
-    ADM_TRY(launch_encode_step(a.x, eps, table, h->step_dev, step, n, st));
+  const long n = (long)d.B * c.in_channels * c.sample_h * Wx;
+  if (d.mode == LOOP_ENCODE) {
+    ADM_TRY(launch_encode_step(d.x, eps, d.coef, h->step_dev, step, n, st));
   } else {
-    SchedStepParams p{a.x, eps, a.step_noise, a.x, a.u8_out, table, h->step_dev, step, a.mask, a.n_steps, a.mask_start,
-                      a.mask_end, a.B, c.in_channels, c.sample_h, Wx};
-    p.noise_step_stride = n; p.u8_step = a.n_steps - 1;
-    p.lo = a.lo; p.hi = a.hi; p.w = a.w; p.max_value = a.max_value; p.scale = h->scale_buf;
-    p.hist = h->hist_buf; p.k_hist_table = h->khist_dev;
-    if (a.encoding_uncond != nullptr) {
-      p.eps_uncond = eps_uncond; p.guidance = a.guidance_scale;
-      p.guidance_rescale = a.guidance_rescale; p.rescale = h->rescale_buf;   // (0: off, the buffer is not touched)
+    SchedStepParams p{d.x, eps, d.step_noise, d.x, d.u8_out, d.coef, h->step_dev, step, d.mask, d.n_steps, d.mask_start,
+                      d.mask_end, d.B, c.in_channels, c.sample_h, Wx};
+    p.noise_step_stride = n; p.u8_step = d.n_steps - 1;
+    p.scale = h->scale_buf; p.hist = h->hist_buf; p.k_hist_table = d.khist;
+    if (d.mode == SCHED_THRESH) { p.lo = d.lo; p.hi = d.hi; p.w = bits_f32(d.w); p.max_value = bits_f32(d.max_value); }
+    if (guided) {
+      p.eps_uncond = eps_uncond; p.guidance = bits_f32(d.guidance_scale);
+      p.guidance_rescale = bits_f32(d.guidance_rescale); p.rescale = h->rescale_buf;   // (0: off, the buffer is not touched)
     }
-    if (a.noise_source == 1) { p.philox = 1; p.nblock = h->noise_blk_dev; }
-    if (a.keep != nullptr) {   // the known-region overwrite: three caller tensors of x's shape (wide when windowed) and the handle's table
-      p.known = a.known; p.known_noise = a.known_noise; p.keep = a.keep; p.known_table = h->known_dev;
-      p.known_batched = a.known_batched != 0; p.keep_batched = a.keep_batched != 0;
+    if (d.noise_blk != nullptr) { p.philox = 1; p.nblock = d.noise_blk; }
+    if (d.keep != nullptr) {   // the known-region overwrite: three caller tensors of x's shape (wide when windowed) and the handle's table
+      p.known = d.known; p.known_noise = d.known_noise; p.keep = d.keep; p.known_table = d.known_tab;
+      p.known_batched = d.known_batched; p.keep_batched = d.keep_batched;
     }
-    if (a.unipc_host != nullptr) {   // the UniPC step: two history slots, then last, in the handle's one buffer
-      p.unipc_table = h->unipc_dev; p.hist = h->unipc_buf; p.last = h->unipc_buf + 2 * n;
-      ADM_TRY(launch_unipc_step(p, a.mode, st, a.prediction));
+    if (d.unipc != nullptr) {   // the UniPC step: two history slots, then last, in the handle's one buffer
+      p.unipc_table = d.unipc; p.hist = h->lazy.unipc; p.last = h->lazy.unipc + 2 * n;
+      ADM_TRY(launch_unipc_step(p, d.mode, st, d.prediction));
     } else {
-      ADM_TRY(launch_sched_step(p, a.mode, st, a.prediction));
+      ADM_TRY(launch_sched_step(p, d.mode, st, d.prediction));
     }
   }
   ADM_TRY(launch_step_advance(h->step_dev, st));
@@ -466,132 +497,91 @@ static int enqueue_step(adm_unet* h, const LoopArgs& a, int step, hipStream_t st
 }
 
 static int run_loop(adm_unet* h, const LoopArgs& a, hipStream_t st) {
-  const adm_sched_coef* coef_host = a.coef_host;
-  const int use_graph = a.use_graph;
-  ADM_TRY(finalize(h));
   ADM_REQUIRE(h->cfg.in_channels == h->cfg.out_channels, "sample_loop: in/out channels differ");
   // the plan's batch: the forwards' (B*nW windows with window_total_w != 0). Every per-plan buffer below is sized by it, and the wide
   // sample's state (history, UniPC state, per-sample factors) lives in the same buffers: nW*W >= Wt and PB >= B
   const int PB = a.B * loop_windows(h, a);
   const size_t plan_elems = (size_t)PB * h->cfg.out_channels * h->cfg.sample_h * h->cfg.sample_w;
-  if (a.window_total_w != 0)
+  const bool guided = a.encoding_uncond != nullptr, windowed = a.window_total_w != 0;
+  if (windowed)
     ADM_REQUIRE((size_t)a.B * h->cfg.out_channels * h->cfg.sample_h * a.window_total_w <= plan_elems,
                 "sample_loop: the wide sample does not fit the buffers of the windows' plan (window_total_w > nW * sample_w)");
   ADM_TRY(plan(h, PB));
-  if (a.encoding_uncond != nullptr && h->eps_uncond_buf == nullptr)
-    ADM_TRY(extra_alloc(h, (void**)&h->eps_uncond_buf, sizeof(float) * plan_elems));
-  if (a.unipc_host != nullptr && h->unipc_buf == nullptr)
-    ADM_TRY(extra_alloc(h, (void**)&h->unipc_buf, sizeof(float) * 3 * plan_elems));
-  if (a.window_total_w != 0) {
-    if (h->win_buf == nullptr) ADM_TRY(extra_alloc(h, (void**)&h->win_buf, sizeof(float) * plan_elems));
-    if (h->wide_eps_buf == nullptr) ADM_TRY(extra_alloc(h, (void**)&h->wide_eps_buf, sizeof(float) * plan_elems));
-    if (a.encoding_uncond != nullptr && h->wide_uncond_buf == nullptr)
-      ADM_TRY(extra_alloc(h, (void**)&h->wide_uncond_buf, sizeof(float) * plan_elems));
+  if (guided) ADM_TRY(ensure(h, &h->lazy.eps_uncond, plan_elems));
+  if (a.unipc_host != nullptr) ADM_TRY(ensure(h, &h->lazy.unipc, 3 * plan_elems));
+  if (windowed) {
+    ADM_TRY(ensure(h, &h->lazy.win, plan_elems));
+    ADM_TRY(ensure(h, &h->lazy.wide_eps, plan_elems));
   }
-#if defined(ADM_EMU)
-  (void)use_graph;
-  ADM_TRY(ensure_coef(h, coef_host, a.n_steps, st));
-  if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, st));
-  if (a.unipc_host != nullptr) ADM_TRY(ensure_unipc(h, a.unipc_host, a.n_steps, st));
-  if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, st));
-  if (a.keep != nullptr) ADM_TRY(ensure_known(h, a.known_coef_host, a.n_steps, st));
-  for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, st));
-  return 0;
-#else
+  if (windowed && guided) ADM_TRY(ensure(h, &h->lazy.wide_uncond, plan_elems));
   hipStream_t run = st;
+#if !defined(ADM_EMU)
   hipEvent_t ev = nullptr;
-  if (use_graph && st == nullptr) {  // the legacy default stream cannot be captured: hop onto an owned stream
+  if (a.use_graph && st == nullptr) {  // the legacy default stream cannot be captured: hop onto an owned stream
     if (!h->own_stream) ADM_HIP_OK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     run = h->own_stream;
     ADM_HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     ADM_HIP_OK(hipEventRecord(ev, st));
     ADM_HIP_OK(hipStreamWaitEvent(run, ev, 0));
   }
-  ADM_TRY(ensure_coef(h, coef_host, a.n_steps, run));
-  if (a.mode == SCHED_MULTISTEP) ADM_TRY(ensure_khist(h, a.k_hist_host, a.n_steps, run));
-  if (a.unipc_host != nullptr) ADM_TRY(ensure_unipc(h, a.unipc_host, a.n_steps, run));
+#endif
+  ADM_TRY(upload_rows(h, &h->coef_dev, &h->coef_cap, a.coef_host, sizeof(adm_sched_coef), a.n_steps, run));
+  ADM_TRY(dmemset(h->step_dev, 0, sizeof(int), run));
+  if (a.mode == SCHED_MULTISTEP) ADM_TRY(upload_rows(h, &h->khist_dev, &h->khist_cap, a.k_hist_host, sizeof(float), a.n_steps, run));
+  if (a.unipc_host != nullptr) ADM_TRY(upload_rows(h, &h->unipc_dev, &h->unipc_cap, a.unipc_host, sizeof(adm_unipc_coef), a.n_steps, run));
   if (a.noise_source == 1) ADM_TRY(ensure_noise_block(h, a, run));
-  if (a.keep != nullptr) ADM_TRY(ensure_known(h, a.known_coef_host, a.n_steps, run));
-  if (!use_graph) {
-    for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, a, s, run));
-  } else {
-    std::vector<uint64_t> key = {(uint64_t)a.x, (uint64_t)a.B, (uint64_t)a.n_steps, (uint64_t)a.step_noise,
-                                 (uint64_t)a.mask, (uint64_t)a.mask_start, (uint64_t)a.mask_end, (uint64_t)a.u8_out,
-                                 (uint64_t)a.mode, (uint64_t)h->coef_dev, (uint64_t)run, (uint64_t)h->net.ctx,
-                                 (uint64_t)h->net.ctx_S, (uint64_t)a.prediction};   // (pred: the kernel itself is baked into the captured node)
-    if (a.mode == SCHED_MULTISTEP) { key.push_back((uint64_t)h->hist_buf); key.push_back((uint64_t)h->khist_dev); }
-    // the UniPC step: another kernel in the captured node, reading the handle's state buffer and table
-    if (a.unipc_host != nullptr) { key.push_back(0x400000000ull); key.push_back((uint64_t)h->unipc_buf); key.push_back((uint64_t)h->unipc_dev); }
-    if (a.mode == SCHED_THRESH) {   // the ranks and the maximum are kernel arguments baked into the captured nodes
-      uint32_t wb, mb;
-      memcpy(&wb, &a.w, 4); memcpy(&mb, &a.max_value, 4);
-      key.push_back((uint64_t)h->scale_buf); key.push_back((uint64_t)a.lo); key.push_back((uint64_t)a.hi);
-      key.push_back(wb); key.push_back(mb);
+  if (a.keep != nullptr) ADM_TRY(upload_rows(h, &h->known_dev, &h->known_cap, a.known_coef_host, 2 * sizeof(float), a.n_steps, run));
+  const StepDesc d = describe_step(h, a, run);
+  if (a.use_graph && memcmp(&d, &h->captured, sizeof d) != 0) {   // nothing captured yet (all zeros), or another step: capture this one
+#if !defined(ADM_EMU)
+    if (h->gexec) {
+      // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
+      // single-step calls in tests/test_pipeline.py): destroying an executable graph under its own replays made that test die with SIGSEGV
+      // inside this call — 4 of 11 runs of test_full_size.py + test_pipeline.py without the drain, 0 of 12 with it.
+      // Re-capture is the rare path; a drain costs nothing there.
+      static const int drain = [] { const char* e = getenv("ADM_GRAPH_DRAIN"); return e ? atoi(e) : 1; }();   // (0: tools/graph_churn_probe.py's A/B)
+      if (drain) (void)stream_sync(h->captured.stream);
+      (void)hipGraphExecDestroy(h->gexec);
+      h->gexec = nullptr;
+      h->captured = {};   // (no graph, no stored step: a failure below leaves the handle with neither)
     }
-    if (a.encoding_uncond != nullptr) {  // the second forward's encoding and output, and the scale: all baked into the captured nodes
-      uint32_t gb;
-      memcpy(&gb, &a.guidance_scale, 4);
-      key.push_back((uint64_t)a.encoding_uncond); key.push_back((uint64_t)h->eps_uncond_buf); key.push_back(0x100000000ull | gb);
-      if (a.guidance_rescale != 0.f) {   // one more captured node (the statistics kernel), phi a kernel argument of the step and the selection
-        uint32_t rb;
-        memcpy(&rb, &a.guidance_rescale, 4);
-        key.push_back(0x300000000ull | rb); key.push_back((uint64_t)h->rescale_buf);
-      }
+    if (h->warm_B != PB) {
+      // One UNCAPTURED forward (into eps_buf; the sample is not touched) before the first capture at this batch size:
+      // the launchers' one-time work — constant buffers (hipMalloc + null-stream copy), hipFuncSetAttribute for the
+      // >64 KiB LDS kernels, device-attribute queries — is not legal inside a stream capture.
+      // Windowed: x holds B wide samples, fewer elements than the PB windows the forward reads: it reads the gathered windows.
+      if (windowed) ADM_TRY(gather_windows(h, d));
+      ADM_TRY(run_forward(h, windowed ? h->lazy.win : d.x, h->eps_buf, PB, d.coef, run));
+      h->warm_B = PB;
     }
-    // the noise stream: the block's address (the handle's, stable) and nothing else; the seed and the row offset are data behind it
-    if (a.noise_source == 1) { key.push_back(0x200000000ull); key.push_back((uint64_t)h->noise_blk_dev); }
-    // the windowed step: two or three more captured nodes, the placement baked into their arguments, and the handle's three buffers
-    if (a.window_total_w != 0) {
-      key.push_back(0x500000000ull); key.push_back((uint64_t)a.window_total_w); key.push_back((uint64_t)a.window_stride);
-      key.push_back((uint64_t)a.window_wrap); key.push_back((uint64_t)h->win_buf); key.push_back((uint64_t)h->wide_eps_buf);
-      key.push_back((uint64_t)h->wide_uncond_buf);
-    }
-    // the known-region overwrite: the three tensors' addresses, the handle's table and the two flags are kernel arguments of the captured
-    // step; what the tensors and the table hold is data behind them (new contents replay the same graph)
-    if (a.keep != nullptr) {
-      key.push_back(0x600000000ull); key.push_back((uint64_t)a.known); key.push_back((uint64_t)a.known_noise); key.push_back((uint64_t)a.keep);
-      key.push_back((uint64_t)h->known_dev); key.push_back((uint64_t)((a.known_batched != 0) | ((a.keep_batched != 0) << 1)));
-    }
-    if (!h->gexec || key != h->gkey) {
-      if (h->gexec) {
-        // the previous loop's replays may still be running (a caller that samples again without a host synchronisation in between — 50
-        // single-step calls in tests/test_pipeline.py): destroying an executable graph under its own replays made that test die with SIGSEGV
-        // inside this call — 4 of 11 runs of test_full_size.py + test_pipeline.py without the drain, 0 of 12 with it.
-        // Re-capture is the rare path; a drain costs nothing there.
-        static const int drain = [] { const char* e = getenv("ADM_GRAPH_DRAIN"); return e ? atoi(e) : 1; }();   // (0: tools/graph_churn_probe.py's A/B)
-        if (drain) (void)stream_sync(h->gstream);
-        (void)hipGraphExecDestroy(h->gexec);
-        h->gexec = nullptr;
-      }
-      if (h->warm_B != PB) {
-        // One UNCAPTURED forward (into eps_buf; the sample is not touched) before the first capture at this batch size:
-        // the launchers' one-time work — constant buffers (hipMalloc + null-stream copy), hipFuncSetAttribute for the
-        // >64 KiB LDS kernels, device-attribute queries — is not legal inside a stream capture.
-        // Windowed: a.x holds B wide samples, fewer elements than the PB windows the forward reads: it reads the gathered windows.
-        if (a.window_total_w != 0) ADM_TRY(gather_windows(h, a, run));
-        ADM_TRY(run_forward(h, a.window_total_w != 0 ? h->win_buf : a.x, h->eps_buf, PB, h->coef_dev, run));
-        h->warm_B = PB;
-      }
-      hipGraph_t graph = nullptr;
-      ADM_HIP_OK(hipStreamBeginCapture(run, hipStreamCaptureModeThreadLocal));
-      int rc = enqueue_step(h, a, 0, run);
-      hipError_t e = hipStreamEndCapture(run, &graph);
-      if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-      ADM_HIP_OK(e);
-      ADM_HIP_OK(hipGraphInstantiate(&h->gexec, graph, nullptr, nullptr, 0));
-      ADM_HIP_OK(hipGraphDestroy(graph));
-      h->gkey = key;
-      h->gstream = run;
-    }
-    for (int s = 0; s < a.n_steps; ++s) ADM_HIP_OK(hipGraphLaunch(h->gexec, run));
+    hipGraph_t graph = nullptr;
+    ADM_HIP_OK(hipStreamBeginCapture(run, hipStreamCaptureModeThreadLocal));
+    int rc = enqueue_step(h, d, 0);
+    hipError_t e = hipStreamEndCapture(run, &graph);
+    if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    ADM_HIP_OK(e);
+    ADM_HIP_OK(hipGraphInstantiate(&h->gexec, graph, nullptr, nullptr, 0));
+    ADM_HIP_OK(hipGraphDestroy(graph));
+#endif
+    h->captured = d;   // (the emulator has no graphs: it remembers and counts the step at the same point, and runs its steps eagerly)
+    ++h->captures;
   }
+#if !defined(ADM_EMU)
+  if (a.use_graph) {
+    for (int s = 0; s < a.n_steps; ++s) ADM_HIP_OK(hipGraphLaunch(h->gexec, run));
+  } else
+#endif
+  {
+    for (int s = 0; s < a.n_steps; ++s) ADM_TRY(enqueue_step(h, d, s));
+  }
+#if !defined(ADM_EMU)
   if (ev) {
     ADM_HIP_OK(hipEventRecord(ev, run));
     ADM_HIP_OK(hipStreamWaitEvent(st, ev, 0));
     ADM_HIP_OK(hipEventDestroy(ev));
   }
-  return 0;
 #endif
+  return 0;
 }
 
 // What every loop entry point does after its own argument checks.
@@ -949,6 +939,8 @@ int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef*
   a.noise_source = 1; a.seed = seed; a.row_offset = row_offset;
   return adm_sample_loop_ex(h, &a, stream);
 }
+
+int adm_unet_loop_captures(adm_unet_t* h) { return h ? h->captures : 0; }
 
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream) {

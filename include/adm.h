@@ -694,7 +694,17 @@ int adm_unet_set_grad_bucket_hook(adm_unet_t* h, int n_buckets, const long* boun
  * Runs n_steps x {UNet forward, scheduler epilogue, mask} on `x` in place and (optionally) the final u8 image.
  * coef_host: n_steps adm_sched_coef (host) including .timestep; step_noise: NULL or device
  * (n_steps,B,C,H,W) noise consumed where k_noise != 0. With use_graph=1 one step is captured into a hipGraph
- * and replayed n_steps times (step-dependent scalars come from a device table indexed by a device counter). */
+ * and replayed n_steps times (step-dependent scalars come from a device table indexed by a device counter).
+ *
+ * What keys the captured step (every loop entry point below refers to this paragraph). A handle holds ONE captured step, keyed by everything its launches were given:
+ * the addresses of the caller's tensors (x, step_noise, mask, u8_out, encoding_uncond, known, known_noise, keep), B, n_steps, mask_start,
+ * mask_end, mode, prediction, the stream, the encoding set on the handle, the addresses of the handle's device tables, and the values of
+ * the features that are ON: lo, hi and the bits of w and max_value in mode 1; the bits of guidance_scale and guidance_rescale with
+ * encoding_uncond; window_stride and window_wrap with window_total_w; the two batched flags with keep. A loop whose key equals the stored
+ * one replays the stored graph, so the following all replay: new CONTENTS at the same addresses (x, the noise, the mask, the encodings, the
+ * known-region tensors), new values in any *_host table of the same n_steps, another seed or row_offset, and any value in a field of a
+ * feature that is off. Any other difference captures again and replaces the stored step, so one handle may alternate between any two
+ * loops; a new plan (another B, adm_unet_set_option) forgets the step as well. use_graph=0 neither uses nor changes it. */
 int adm_sample_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                     const float* step_noise, const float* mask, int mask_start, int mask_end,
                     uint8_t* u8_out, int use_graph, void* stream);
@@ -711,8 +721,8 @@ int adm_sample_loop_thresholded(adm_unet_t* h, float* x, int B, const adm_sched_
                                 const float* step_noise, const float* mask, int mask_start, int mask_end,
                                 uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value);
 /* adm_sample_loop / adm_sample_loop_thresholded for a model of the given `prediction` (0 epsilon, 1 sample, 2 v_prediction; adm_sched_step_pred;
- * adm_version() >= 111). thresholded == 0: the static clamp, and lo, hi, w, max_value are ignored. The prediction type is part of the captured
- * graph's key: one handle may alternate between types. */
+ * adm_version() >= 111). thresholded == 0: the static clamp, and lo, hi, w, max_value are ignored. One handle may alternate between types
+ * ("what keys the captured step" above). */
 int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                          const float* step_noise, const float* mask, int mask_start, int mask_end,
                          uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
@@ -723,8 +733,8 @@ int adm_sample_loop_pred(adm_unet_t* h, float* x, int B, const adm_sched_coef* c
  * batch B on the same plan, the second with the encoding pointer swapped and into a second output buffer that the handle allocates with its
  * plan on the first guided call at a batch size, then one guided step kernel; all inside the one captured step. A sample's bits do not
  * depend on its batch, and encoding_uncond_dev equal to the set encoding gives the unguided loop's bits. k_hist_host != NULL: the multistep
- * loop (k_hist_host[0] == 0, prediction == 0, thresholded == 0); otherwise as adm_sample_loop_pred. The two encodings, the second buffer
- * and the bits of guidance_scale are part of the captured graph's key. The handle's encoding is unchanged on return. */
+ * loop (k_hist_host[0] == 0, prediction == 0, thresholded == 0); otherwise as adm_sample_loop_pred. The handle's encoding is unchanged on
+ * return. */
 int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, const float* k_hist_host, int n_steps,
                            const float* step_noise, const float* mask, int mask_start, int mask_end,
                            uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
@@ -733,9 +743,8 @@ int adm_sample_loop_guided(adm_unet_t* h, float* x, int B, const adm_sched_coef*
  * 113): no noise tensor, whatever n_steps. row_offset: the global row of x[0] (a shard's first row). encoding_uncond_dev == NULL: unguided,
  * and the model may be unconditional; otherwise as adm_sample_loop_guided. The handle owns a 16-byte device block {seed_lo, seed_hi,
  * row_offset, stream id} that the step kernel reads through a pointer, as it reads the step index; this call rewrites it with a
- * stream-ordered copy before the first step, outside the captured step. The captured graph's key gains that block's address (stable for
- * the life of the handle) and nothing else: another seed or another row_offset replays the same graph. Every coef_host[i].timestep must be
- * in [0, 2^31). */
+ * stream-ordered copy before the first step, outside the captured step: another seed or another row_offset replays the same graph (the block's
+ * address is stable for the life of the handle). Every coef_host[i].timestep must be in [0, 2^31). */
 int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps,
                            const float* mask, int mask_start, int mask_end,
                            uint8_t* u8_out, int use_graph, void* stream, int lo, int hi, float w, float max_value,
@@ -769,27 +778,30 @@ typedef struct adm_sample_loop_args {
   float guidance_rescale;    /* adm_version() >= 115: "guidance rescale" above; 0: off; otherwise needs encoding_uncond */
   const adm_unipc_coef* unipc_host;   /* adm_version() >= 116: NULL, or n_steps host rows: the UniPC loop ("UniPC" above; mode 0 or 1, any
                                 prediction, step_noise NULL and noise_source 0). Row 0 must have c_t == 0 && p_m1 == 0 (a run starts
-                                without state). The handle owns `last` and the two history slots; their address joins the captured
-                                graph's key as the multistep history's does */
+                                without state). The handle owns `last` and the two history slots */
   int window_total_w, window_stride, window_wrap;   /* adm_version() >= 117: "Windowed sampling" above. window_total_w == 0: off, and the
                                 other two are ignored. Otherwise x and u8_out are (B,C,sample_h,window_total_w), step_noise is
                                 (n_steps,B,C,sample_h,window_total_w), B counts WIDE samples, the handle is planned at batch B*nW (its
                                 encodings have B*nW rows, sample-major) and one captured step is: gather into a handle-owned window
                                 buffer, the forward(s) at batch B*nW, one blend per forward output into handle-owned wide buffers, the
-                                step at W = window_total_w, the counter's increment. The three fields and those buffers' addresses are
-                                part of the captured graph's key: one handle may alternate windowed and ordinary loops. Refused by
-                                name: mask != NULL, and every placement rule (window_total_w, window_stride, window_wrap) */
+                                step at W = window_total_w, the counter's increment. One handle may alternate windowed and ordinary
+                                loops. Refused by name: mask != NULL, and every placement rule (window_total_w, window_stride,
+                                window_wrap) */
   const float* known;        /* adm_version() >= 118: "Region in-painting" above, as adm_sched_step_args; with window_total_w the three */
-  const float* known_noise;  /* tensors have the wide shape. The three pointers, the handle's device copy of the table and the two flags */
-  const uint8_t* keep;       /* are part of the captured graph's key: new contents at the same addresses replay the same graph, and one */
-  const float* known_coef_host;   /* handle may alternate loops with and without it. known_coef_host: n_steps x 2 HOST floats (ka, kb), */
-  int known_batched, keep_batched;   /* row i beside coef_host[i]. keep == NULL: off. Refused by name as in adm_sched_step_ex */
+  const float* known_noise;  /* tensors have the wide shape. One handle may alternate loops with and without it. known_coef_host: */
+  const uint8_t* keep;       /* n_steps x 2 HOST floats (ka, kb), row i beside coef_host[i]. keep == NULL: off, and the other five are */
+  const float* known_coef_host;   /* ignored. Refused by name as in adm_sched_step_ex */
+  int known_batched, keep_batched;
 } adm_sample_loop_args;
 int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 /* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
  *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream);
+/* Test aid (adm_version() >= 122): how many times this handle has captured a step since it was created (0 for NULL). The emulation build
+ * has no graphs and runs every step eagerly; it keeps the key and counts at the same point, so "what keys the captured step" above is
+ * checked on both builds (tests/test_loop_graph_key.py). */
+int adm_unet_loop_captures(adm_unet_t* h);
 
 /* ---------------------------------------------------------------- AutoencoderKL executor (rows V1-V3, config 4)
  * Replaces `vqvae.encode(x).latent_dist.sample(generator)` (pipeline_audio_diffusion.py:144; train_unet.py:104,233)
