@@ -208,6 +208,8 @@ _SIGS = {
                                          C.c_void_p, C.c_float, C.c_uint64, C.c_int]),
     "adm_sample_loop_ex": (C.c_int, [C.c_void_p, C.POINTER(SampleLoopArgs), C.c_void_p]),
     "adm_encode_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SchedCoef), C.c_int, C.c_int, C.c_void_p]),
+    "adm_encode_loop_ex": (C.c_int, [C.c_void_p, C.POINTER(SampleLoopArgs), C.c_void_p]),
+    "adm_encode_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]),
     "adm_unet_loop_captures": (C.c_int, [C.c_void_p]),
 }
 # entry points added by later translation units (k_mel.hip); bound when present in the header AND the library

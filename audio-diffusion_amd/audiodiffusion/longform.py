@@ -5,6 +5,7 @@ heavy parts are batched on the device:
 
 * `interpolate`    — cells 32-37 / 41-46: DDIM-invert two spectrograms (ONE batched `encode`), spherical interpolation for a
                      whole grid of weights (`ops.slerp_grid`, one launch pair), ONE batched sampling of all of them.
+* `invert_audio`   — not in the notebook: audio -> the noise behind it (`encode`), a clip longer than one slice in ONE windowed call.
 * `outpaint`       — cell 16: extend a clip segment by segment; every new segment is generated with its first
                      `overlap_secs` pinned to the tail of the previous one (`mask_start_secs`): the per-step mask overwrite
                      is part of the captured denoising graph (csrc/k_sched.hip `sched_step_kernel`, every instantiation), not a Python loop.
@@ -38,12 +39,41 @@ def slerp_grid(x0: torch.Tensor, x1: torch.Tensor, alphas: Sequence[float]) -> t
 
 @torch.no_grad()
 def interpolate(pipe, image_a: Image.Image, image_b: Image.Image, alphas: Sequence[float], steps: int = None,
-                encode_steps: int = 50, generator: torch.Generator = None, audio: bool = True, init_phases=None):
-    """Returns (images, (sample_rate, audios)) with one entry per alpha (notebook cells 32-37)."""
-    noise = pipe.encode([image_a, image_b], steps=encode_steps)          # both inversions in one batched loop
+                encode_steps: int = 50, generator: torch.Generator = None, audio: bool = True, init_phases=None, *,
+                level: str = None, encoding: torch.Tensor = None, window_stride: int = None, circular: bool = False):
+    """Returns (images, (sample_rate, audios)) with one entry per alpha (notebook cells 32-37). `level`, `encoding`, `window_stride`,
+    `circular`: as `AudioDiffusionPipeline.encode`. The encoding ((1, S, D) or (S, D): one condition for the whole grid) serves both
+    inversions and the sampling; images wider than the model are inverted and sampled through the windowed loop at one placement."""
+    noise = pipe.encode([image_a, image_b], steps=encode_steps, level=level, encoding=encoding, window_stride=window_stride,
+                        circular=circular)                                 # both inversions in one batched loop
     grid = slerp_grid(noise[0], noise[1], alphas)                          # (A, C, H, W)
+    call = {}
+    if encoding is not None:
+        enc = encoding[None] if encoding.dim() == 2 else encoding
+        if enc.shape[0] != 1:
+            raise ValueError(f"interpolate takes ONE encoding, (1, S, D) or (S, D), for both images and every alpha, not {tuple(encoding.shape)}")
+        call["encoding"] = enc.expand(len(alphas), -1, -1)
+    if noise.shape[3] > pipe.unet._hw()[1]:   # wide: the sampler takes the same placement
+        call.update(frames=int(noise.shape[3]), window_stride=window_stride, circular=circular)
     return pipe(batch_size=len(alphas), noise=grid, steps=steps, generator=generator, return_dict=False, audio=audio,
-                init_phase=init_phases)
+                init_phase=init_phases, **call)
+
+
+@torch.no_grad()
+def invert_audio(pipe, raw_audio: np.ndarray, **encode_kwargs):
+    """DDIM-invert a clip: `raw_audio` becomes ONE spectrogram image and goes through `pipe.encode(**encode_kwargs)`. A clip of at most
+    one slice gives the model-width image of the pipeline's own Mel; a longer one gives an image as wide as the clip (hop_length samples
+    per column, rounded down to whole cells of 4 columns of the tensor being inverted), made by a Mel of the pipeline's config with
+    x_res = that width (`_wide_mel`), so the whole clip inverts in ONE windowed call (`window_stride`, `circular` of `encode` place the
+    windows and the width must fit them). Returns (the recovered noise, the image)."""
+    mel = pipe.mel
+    cell = 4 * _cell(pipe)
+    cols = len(raw_audio) // mel.hop_length // cell * cell
+    if cols > mel.x_res:
+        mel = pipe._wide_mel(cols)
+    mel.load_audio(raw_audio=raw_audio)
+    image = mel.audio_slice_to_image(0)
+    return pipe.encode([image], **encode_kwargs), image
 
 
 def _one(pipe, **kw):

@@ -243,6 +243,19 @@ def sched_step(x, eps, coef_table, step, noise=None, mask=None, mask_start=0, ma
     return out
 
 
+def encode_step(x, model_out, coef_table, step, prediction=0, step_dev=None):
+    """One DDIM inversion step on x IN PLACE (csrc/k_sched.hip `encode_step_kernel`; include/adm.h "DDIM inversion" names the fields of a
+    row; `DDIMScheduler.encode_rows` builds them), one native call (`adm_encode_step`). x, model_out: the same shape, numel % 4 == 0;
+    model_out is the output of an epsilon (0), sample (1) or v_prediction (2) model. step_dev: optional int32 device scalar that
+    replaces `step`. -> x"""
+    _f32(x), _f32(model_out), _f32(coef_table)
+    assert model_out.shape == x.shape and model_out.device == x.device
+    assert coef_table.dim() == 2 and coef_table.shape[1] == 8 and (step_dev is not None or 0 <= int(step) < coef_table.shape[0])
+    N.check(N.lib().adm_encode_step(N.ptr(x), N.ptr(model_out), N.ptr(coef_table), N.ptr(step_dev), int(step), int(prediction),
+                                    x.numel(), N.stream_for(x)))
+    return x
+
+
 def sched_multistep(x, eps, coef_table, k_hist_table, hist, step, noise=None, mask=None, mask_start=0, mask_end=0, out=None,
                     u8_out=None, step_dev=None, uncond=None, guidance_scale=None, guidance_rescale=None, rescale_out=None, known=None):
     """Fused multistep scheduler epilogue (csrc/k_sched.hip `sched_step_kernel<SCHED_MULTISTEP, ...>`). x, eps, hist: (B,C,H,W); k_hist_table: (n,)

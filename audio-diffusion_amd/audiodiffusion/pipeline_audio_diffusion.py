@@ -648,31 +648,83 @@ class AudioDiffusionPipeline(DiffusionPipeline):
             return images, (self.mel.get_sample_rate(), audios)
         return PipelineOutput(audios=np.array(audios)[:, np.newaxis, :] if audio else np.zeros((0, 1, 0)), images=images)
 
+    def _encode_encoding(self, encoding, B):
+        """The rules of `encode(encoding=...)`, before any work: required for a conditional model, refused for an unconditional one,
+        (B, S, D) or (1, S, D) broadcast over the batch. -> None, or the (B, S, D) fp32 tensor."""
+        if not isinstance(self.unet, UNet2DConditionModel):
+            if encoding is not None:
+                raise ValueError("`encoding` conditions a UNet2DConditionModel: this pipeline's unet is unconditional")
+            return None
+        if encoding is None:
+            raise ValueError("encode() with a UNet2DConditionModel needs the `encoding` the images are to be inverted under: none was given")
+        D = self.unet.config.cross_attention_dim
+        enc = encoding[:, None, :] if torch.is_tensor(encoding) and encoding.dim() == 2 else encoding
+        if not torch.is_tensor(enc) or enc.dim() != 3 or enc.shape[0] not in (1, B) or enc.shape[2] != D:
+            got = tuple(encoding.shape) if torch.is_tensor(encoding) else type(encoding).__name__
+            raise ValueError(f"encoding shape {got} is not (B, S, D) or (1, S, D) with B = {B}, D = {D}")
+        return enc.to(self.device, torch.float32).expand(B, -1, -1)
+
     @torch.no_grad()
-    def encode(self, images: List[Image.Image], steps: int = 50) -> torch.Tensor:
-        """Reverse step process: recover noisy image from generated image (`pipeline_audio_diffusion.py:207-242`)."""
+    def encode(self, images: List[Image.Image], steps: int = 50, *, level: str = None, encoding: torch.Tensor = None,
+               window_stride: int = None, circular: bool = False, generator: torch.Generator = None) -> torch.Tensor:
+        """Reverse step process: recover noisy image from generated image (`pipeline_audio_diffusion.py:207-242`).
+
+        `encode(images, steps)` is the reference's procedure. Not in the reference (defaults reproduce it), for every model family the
+        sampler runs; the result has the shape and scale `pipe(noise=...)` takes for this pipeline:
+          * `prediction_type` "sample" / "v_prediction": the same native loop with the inversion step of that type. These two have no
+            default `level`: without one the call raises the NotImplementedError it always raised, which asks for the rule by name.
+          * `level`: None is "reference" for an epsilon model. "reference" gives the model the TARGET timestep of each step, as the reference does; "matched" gives it the
+            timestep of the level the sample is at (textbook DDIM inversion; `DDIMScheduler.encode_rows`). On a zero-terminal-SNR
+            schedule use "matched": the last "reference" row is finite but degenerate.
+          * `encoding` (B, S, D), or (1, S, D) broadcast: required for a UNet2DConditionModel, a ValueError for an unconditional model.
+            Guidance is not offered: guided inversion is a different, unstable procedure.
+          * with a `vqvae` the images go through `vqvae.encode` and `* 0.18215` and the latent is inverted: the posterior's `.mode()`
+            with `generator=None` (inversion is then deterministic), `.sample(generator=generator)` otherwise, the rule of `__call__`.
+          * images wider than the model, in cells of the tensor being inverted (image columns; f = 2^(VAE blocks - 1) of them with a
+            `vqvae`), are inverted through the windowed loop (include/adm.h "Windowed sampling"): `window_stride` (default W // 2) and
+            `circular` place the windows by the rules and with the messages of `__call__(frames=...)`; with a `vqvae` the wide image goes
+            through `vqvae.encode_tiled` at that placement. `window_stride` or `circular` with a model-width image: ValueError.
+        Every rule is checked before any native call."""
         # Only works with DDIM as this method is deterministic
         assert isinstance(self.scheduler, DDIMScheduler)
-        if self.scheduler.config.prediction_type != "epsilon":
-            raise NotImplementedError(f"encode() is not implemented for prediction_type={self.scheduler.config.prediction_type!r} "
-                                      f"(epsilon only)")
-        if isinstance(self.unet, UNet2DConditionModel):   # the reference calls self.unet(sample, t) here (:237): no encoding
-            raise NotImplementedError("encode() is defined for the unconditional UNet2DModel only, as in the reference")
+        level = self.scheduler._encode_level(level)
         self.scheduler.set_timesteps(steps)
+        rows = self.scheduler.encode_rows(level)
         sample = np.array(
             [np.frombuffer(image.tobytes(), dtype="uint8").reshape((1, image.height, image.width)) for image in images]
         )
         sample = (sample / 255) * 2 - 1
+        f = self._vae_factor()
+        B, _, H, W = sample.shape
+        if H % f or W % f:
+            raise ValueError(f"images of {H} x {W} pixels are not whole latent cells of {f} x {f} pixels")
+        H, W = H // f, W // f   # in cells of the tensor being inverted
+        enc = self._encode_encoding(encoding, B)
+        mh, mw = self.unet._hw()
+        window = self._window(W if W > mw else None, window_stride, circular)
+        if window is not None and H != mh:
+            raise ValueError(f"a wide sample has the model's height {mh}, not {H}")
         sample = torch.Tensor(sample).to(self.device).contiguous()
-        rows = self.scheduler.encode_rows()
+        if self.vqvae is not None:
+            if window is None:
+                dist = self.vqvae.encode(sample).latent_dist
+            else:
+                dist = self.vqvae.encode_tiled(sample, f * mw, f * window[1], window[2]).latent_dist
+            sample = (0.18215 * (dist.mode() if generator is None else dist.sample(generator=generator))).contiguous()
         coef = (N.SchedCoef * len(rows))(*[N.SchedCoef(*[float(r[k]) for k in
                                            ("sqrt_beta", "sqrt_alpha", "clip", "k_x0", "k_x", "k_eps", "k_noise", "timestep")])
                                            for r in rows])
         B, _, H, W = sample.shape
-        if tuple(self.unet._hw()) != (H, W):
+        nW = 1 if window is None else window[3]
+        if window is None and (mh, mw) != (H, W):
             self.unet.sample_size = (H, W)
         h = self.unet._ensure_handle()
-        N.check(N.lib().adm_encode_loop(h, N.ptr(sample), B, coef, len(rows), 1, N.stream_for(sample)))
+        if enc is not None:   # set on the handle as `__call__` does: the rows of sample b serve its nW windows, sample-major
+            self.unet._set_encoding(h, enc.repeat_interleave(nW, dim=0) if nW > 1 else enc, B * nW, sample.device)
+        args = N.SampleLoopArgs(x=N.ptr(sample), B=B, coef_host=coef, n_steps=len(rows), use_graph=1, prediction=self.scheduler.prediction)
+        if window is not None:
+            args.window_total_w, args.window_stride, args.window_wrap = W, window[1], int(window[2])
+        N.check(N.lib().adm_encode_loop_ex(h, args, N.stream_for(sample)))
         return sample
 
     @staticmethod

@@ -352,19 +352,52 @@ class DDIMScheduler(_SchedulerBase):
                              k_noise=float(std) if eta > 0 else 0.0, timestep=float(t)))
         return rows
 
-    def encode_rows(self):
-        """Coefficients of the DDIM inversion update, `pipeline_audio_diffusion.py:228-240`, in loop order
-        (ascending timesteps): x = (x - c_dir*eps) * a_prev^-0.5 * a_t^0.5 + b_t^0.5 * eps."""
-        if self.config.prediction_type != "epsilon":
-            # the reference's inversion uses the model output as eps at a mismatched noise level; not generalised to the other types
-            raise NotImplementedError(f"encode() is not implemented for prediction_type={self.config.prediction_type!r} (epsilon only)")
+    ENCODE_LEVELS = ("reference", "matched")
+
+    def _encode_level(self, level):
+        """`level=None`: "reference" for an epsilon model, the call as it always was; the other two prediction types have no default and
+        keep the NotImplementedError they always gave, which now asks for the rule by name."""
+        if level is None:
+            if self.config.prediction_type != "epsilon":
+                raise NotImplementedError(f"encode() has no default `level` for prediction_type={self.config.prediction_type!r}: the "
+                                          f"reference's rule uses the model output at a mismatched noise level. Pass level='matched' "
+                                          f"(the model is given the sample's own timestep) or level='reference' (the reference's rule)")
+            return "reference"
+        if level not in self.ENCODE_LEVELS:
+            raise ValueError(f"level={level!r} must be one of {self.ENCODE_LEVELS}")
+        return level
+
+    def encode_rows(self, level=None):
+        """Rows of the DDIM inversion update in loop order (ascending timesteps; include/adm.h "DDIM inversion" names the fields). With
+        s = `_prev_acp(t)` the level the sample has, t the target level, c the level of the timestep the model is given and e the noise
+        prediction formed from the model output at c (the table of `coef_rows`' prediction types):
+            x' = (x - sqrt(1 - s)*e) * s^-0.5 * t^0.5 + sqrt(1 - t)*e
+        level="reference": the reference's rule (`pipeline_audio_diffusion.py:228-240`): the model is given the TARGET timestep t and
+            c = t, although the sample sits at s: a first-order error. For an epsilon model these are the reference's rows, bit for bit.
+        level="matched": textbook DDIM inversion: the model is given the sample's own timestep max(t - T // N, 0) and c is
+            alphas_cumprod there. On the first row s may be `final_alpha_cumprod` = 1: x0 = x exactly, and nothing divides by zero.
+        level=None (default): "reference" for an epsilon model; a NotImplementedError naming `prediction_type` for the other two, as before
+            they were built: for them the rule is to be named.
+        All three prediction types, every `timestep_spacing` and `rescale_betas_zero_snr` are accepted (an epsilon model on a zero-SNR
+        row stays refused, as in sampling). On a zero-terminal-SNR schedule the last "reference" row is finite but degenerate: the
+        model is evaluated where its output says nothing about the noise (e = x for a sample or v model, so x' = x): use "matched"."""
+        level = self._encode_level(level)
+        ts = torch.flip(self.timesteps, (0,)).tolist()
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        given = ts if level == "reference" else [max(t - ratio, 0) for t in ts]
+        self._refuse_epsilon_at_zero_snr(ts)
+        if self.config.prediction_type == "sample":     # (its e divides by sqrt(1 - c))
+            self._refuse_epsilon_at_zero_snr(given)
+        eps = self.config.prediction_type == "epsilon"  # reads no conversion pair: its rows keep the zeros they had
         rows = []
-        for t in torch.flip(self.timesteps, (0,)).tolist():
+        for t, tc in zip(ts, given):
             a_t = self.alphas_cumprod[t]
             a_prev = self._prev_acp(t)
+            a_c = self.alphas_cumprod[tc]
             b_t = 1 - a_t
             rows.append(dict(sqrt_beta=float((1 - a_prev) ** 0.5), sqrt_alpha=float(a_prev ** (-0.5)), clip=-1.0,
-                             k_x0=float(a_t ** 0.5), k_x=0.0, k_eps=float(b_t ** 0.5), k_noise=0.0, timestep=float(t)))
+                             k_x0=float(a_t ** 0.5), k_x=0.0 if eps else float(a_c ** 0.5), k_eps=float(b_t ** 0.5),
+                             k_noise=0.0 if eps else float((1 - a_c) ** 0.5), timestep=float(tc)))
         return rows
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,

@@ -38,7 +38,8 @@ int launch_sched_threshold(const SchedStepParams& p, hipStream_t st, int pred = 
 int launch_guidance_stats(const SchedStepParams& p, hipStream_t st, const char* who);   // the rescale factors alone: p.rescale[b] = r_b (nothing when p.guidance_rescale == 0)
 // k_unipc.hip: statistics (guidance_rescale != 0) -> selection (mode SCHED_THRESH) -> unipc_step_kernel, on the one stream
 int launch_unipc_step(const SchedStepParams& p, int mode, hipStream_t st, int pred = PRED_EPSILON);
-int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
+// the DDIM inversion step on n elements, in place (include/adm.h "DDIM inversion"); eps is the model output of a `pred` model
+int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, int pred, long n,
                        hipStream_t st);
 int launch_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,
                      int cn, float* out, int B, int N, long P, hipStream_t st);

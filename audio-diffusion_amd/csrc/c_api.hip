@@ -40,7 +40,7 @@ struct AdmSegvInstall {
 
 extern "C" {
 
-int adm_version(void) { return 122; }   // 122: test aid adm_unet_loop_captures (how often a handle has captured a step of the sampling loop); 121: adm_window_crossfade (the weighted join of a tiled codec's windows, csrc/k_window.hip) and adm_vae_sample_moments (adm_vae_encode's sampling tail as a launch of its own): AutoencoderKL.decode_tiled / encode_tiled, windowed sampling with a vqvae; 120: test aids adm_conv2d_gn_finish (a convolution announced as the executors announce it when a GroupNorm reads its output) and adm_last_conv_detail (what the fp32 implicit-GEMM / small-channel launchers chose: cout tile, split, finish kernel, tap mask, pixel tile); 119: test aid adm_mel_last_variant; 118: adm_sched_step_args.known / .known_noise / .keep / .known_table / .known_batched / .keep_batched, adm_sample_loop_args the same with .known_coef_host (region in-painting: the known-region overwrite under an arbitrary keep mask inside the step kernels, csrc/k_sched_common.h sched_known4; no new symbol); 117: adm_window_gather / adm_window_blend, adm_sample_loop_args.window_total_w / .window_stride / .window_wrap (windowed sampling: wide and circular spectrograms through overlapping model-sized windows in the captured loop, csrc/k_window.hip; no new loop symbol); 116: adm_unipc_coef, adm_sched_step_args.unipc_table / .last, adm_sample_loop_args.unipc_host (the UniPC predictor-corrector step and loop, csrc/k_unipc.hip; no new symbol); 115: adm_sched_step_args.guidance_rescale / .rescale, adm_sample_loop_args.guidance_rescale (rescaled classifier-free guidance; no new symbol); 114: adm_sched_step_args / adm_sample_loop_args and adm_sched_step_ex / adm_sched_threshold_ex / adm_sample_loop_ex (one struct-argument entry point per family; the positional ones are frozen); 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
+int adm_version(void) { return 123; }   // 123: adm_encode_step / adm_encode_loop_ex (DDIM inversion for the three prediction types, conditional models and the windowed loop; an inversion row carries the conversion pair (sa_c, sb_c) in k_x / k_noise; adm_encode_loop is frozen and calls adm_encode_loop_ex); 122: test aid adm_unet_loop_captures (how often a handle has captured a step of the sampling loop); 121: adm_window_crossfade (the weighted join of a tiled codec's windows, csrc/k_window.hip) and adm_vae_sample_moments (adm_vae_encode's sampling tail as a launch of its own): AutoencoderKL.decode_tiled / encode_tiled, windowed sampling with a vqvae; 120: test aids adm_conv2d_gn_finish (a convolution announced as the executors announce it when a GroupNorm reads its output) and adm_last_conv_detail (what the fp32 implicit-GEMM / small-channel launchers chose: cout tile, split, finish kernel, tap mask, pixel tile); 119: test aid adm_mel_last_variant; 118: adm_sched_step_args.known / .known_noise / .keep / .known_table / .known_batched / .keep_batched, adm_sample_loop_args the same with .known_coef_host (region in-painting: the known-region overwrite under an arbitrary keep mask inside the step kernels, csrc/k_sched_common.h sched_known4; no new symbol); 117: adm_window_gather / adm_window_blend, adm_sample_loop_args.window_total_w / .window_stride / .window_wrap (windowed sampling: wide and circular spectrograms through overlapping model-sized windows in the captured loop, csrc/k_window.hip; no new loop symbol); 116: adm_unipc_coef, adm_sched_step_args.unipc_table / .last, adm_sample_loop_args.unipc_host (the UniPC predictor-corrector step and loop, csrc/k_unipc.hip; no new symbol); 115: adm_sched_step_args.guidance_rescale / .rescale, adm_sample_loop_args.guidance_rescale (rescaled classifier-free guidance; no new symbol); 114: adm_sched_step_args / adm_sample_loop_args and adm_sched_step_ex / adm_sched_threshold_ex / adm_sample_loop_ex (one struct-argument entry point per family; the positional ones are frozen); 113: adm_randn / adm_sched_step_philox / adm_sample_loop_philox (noise drawn in the step kernel: "adm noise stream 1"); 112: adm_sched_threshold_guided / adm_sched_step_guided / adm_sample_loop_guided (classifier-free guidance); 111: adm_sched_step_pred / adm_sched_threshold_pred / adm_sample_loop_pred / adm_noise_and_velocity (sample and v_prediction models); 110: adm_sched_threshold / adm_sched_step_thresholded / adm_sample_loop_thresholded (dynamic thresholding of x0); 109: adm_sched_multistep / adm_sample_loop_multistep (second-order multistep scheduler step and loop); 108: option "wgrad_path", test aids adm_last_wgrad_variant / adm_wgrad_reduce; 107: test aids adm_time_embedding / adm_temb_proj; 106: adm_last_attention_variant; 105: option "side_overlap", adm_unet_plan_ops / adm_vae_plan_ops (adm_plan_op)
 //   // 104 (round 6): adm_conv_args.single_sample, option "single_sample"; 103 (round 6): adm_conv_args.wino6_rule, adm_unet_set_option, adm_release_stream
 //   // 102 (round 5): Winograd buffers hold two images (adm_winograd_packed_floats)
 //   // 101 (round 4): adm_slerp_grid takes double weights (round 3), blocked-image entry points
@@ -269,6 +269,12 @@ int adm_sched_step_philox(const float* x, const float* eps_cond, const float* ep
   sched_args_threshold(a, lo, hi, w, max_value, scale);
   a.noise_source = 1; a.seed = seed; a.row_offset = row_offset;
   return adm_sched_step_ex(&a, stream);
+}
+
+int adm_encode_step(float* x, const float* model_out, const adm_sched_coef* coef_table, const int* step_dev, int step, int prediction,
+                    long n, void* stream) {
+  ADM_REQUIRE(x && model_out && coef_table, "encode_step: null argument");
+  return launch_encode_step(x, model_out, coef_table, step_dev, step, prediction, n, (hipStream_t)stream);
 }
 
 int adm_add_noise(const float* x0, long x0_bstride, const float* noise, const float* sa, const float* sb, int cb,

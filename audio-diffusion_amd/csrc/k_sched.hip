@@ -407,11 +407,17 @@ __global__ void __launch_bounds__(kStatsThreads) guidance_stats_kernel(const flo
 
 __global__ void step_advance_kernel(int* step_dev) { *step_dev += 1; }
 
-// DDIM inversion update (pipeline_audio_diffusion.py:238-240).
+// DDIM inversion update (pipeline_audio_diffusion.py:238-240), in place, for the three prediction types (include/adm.h "DDIM inversion"
+// names the fields of a row). PRED changes one line: e, the noise prediction, is sched_eps of the model output at the level the model
+// was given, (sa_c, sb_c) = (k_x, k_noise) of the row; the epsilon instantiation reads neither and keeps the reference's two expressions
+// and their rounding order. 12 B/elem: x and the model output in, x out.
+template <int PRED>
 __global__ void __launch_bounds__(256) encode_step_kernel(float* x, const float* __restrict__ eps,
                                                           const adm_sched_coef* __restrict__ table,
                                                           const int* __restrict__ step_dev, int step, long n4) {
   const adm_sched_coef c = table[step_dev ? *step_dev : step];
+  adm_sched_coef cc = c;   // the row as sched_eps reads it: the conversion pair where a sampling row has (sa, sb)
+  cc.sqrt_alpha = c.k_x; cc.sqrt_beta = c.k_noise;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 xv = reinterpret_cast<const float4*>(x)[i];
@@ -420,8 +426,9 @@ __global__ void __launch_bounds__(256) encode_step_kernel(float* x, const float*
     const float* es = reinterpret_cast<const float*>(&ev);
     ADM_UNROLL
     for (int k = 0; k < 4; ++k) {
-      float s = (xs[k] - c.sqrt_beta * es[k]) * c.sqrt_alpha;
-      xs[k] = s * c.k_x0 + c.k_eps * es[k];
+      const float e = sched_eps<PRED>(xs[k], es[k], es[k], cc);   // (a sample model's output is its x0)
+      float s = (xs[k] - c.sqrt_beta * e) * c.sqrt_alpha;
+      xs[k] = s * c.k_x0 + c.k_eps * e;
     }
     reinterpret_cast<float4*>(x)[i] = xv;
   }
@@ -580,10 +587,16 @@ int launch_step_advance(int* step_dev, hipStream_t st) {
   return ADM_CHECK_LAUNCH();
 }
 
-int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, long n,
+int launch_encode_step(float* x, const float* eps, const adm_sched_coef* table, const int* step_dev, int step, int pred, long n,
                        hipStream_t st) {
-  ADM_REQUIRE(n % 4 == 0, "encode_step: size must be a multiple of 4");
-  ADM_LAUNCH(encode_step_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, eps, table, step_dev, step, n / 4);
+  ADM_REQUIRE(n > 0 && n % 4 == 0, "encode_step: size must be a positive multiple of 4");
+  ADM_REQUIRE(pred >= PRED_EPSILON && pred <= PRED_V, "encode_step: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  ADM_REQUIRE(step_dev != nullptr || step >= 0, "encode_step: step must be >= 0 (or step_dev given)");
+  using EncodeKernel = void (*)(float*, const float*, const adm_sched_coef*, const int*, int, long);
+  static constexpr EncodeKernel kEncodeKernels[3] = {encode_step_kernel<PRED_EPSILON>, encode_step_kernel<PRED_SAMPLE>,
+                                                     encode_step_kernel<PRED_V>};
+  const EncodeKernel kernel = kEncodeKernels[pred];
+  ADM_LAUNCH(kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, eps, table, step_dev, step, n / 4);
   return ADM_CHECK_LAUNCH();
 }
 

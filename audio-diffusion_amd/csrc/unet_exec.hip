@@ -376,7 +376,7 @@ static int upload_rows(adm_unet* h, T** dev, int* cap, const T* host, size_t row
 }
 
 // adm_sample_loop_args::mode inside this file: the SCHED_* mode of the step that follows the forward, or the DDIM inversion step
-// (adm_encode_loop only; adm_sample_loop_ex refuses it)
+// (adm_encode_loop_ex sets it; adm_sample_loop_ex refuses it)
 enum { LOOP_ENCODE = -1 };
 using LoopArgs = adm_sample_loop_args;
 // LoopArgs::encoding_uncond and guidance_scale: classifier-free guidance (the unconditional encoding, device, of the shape of the handle's).
@@ -469,7 +469,7 @@ static int enqueue_step(adm_unet* h, const StepDesc& d, int step) {
   }
   const long n = (long)d.B * c.in_channels * c.sample_h * Wx;
   if (d.mode == LOOP_ENCODE) {
-    ADM_TRY(launch_encode_step(d.x, eps, d.coef, h->step_dev, step, n, st));
+    ADM_TRY(launch_encode_step(d.x, eps, d.coef, h->step_dev, step, d.prediction, n, st));
   } else {
     SchedStepParams p{d.x, eps, d.step_noise, d.x, d.u8_out, d.coef, h->step_dev, step, d.mask, d.n_steps, d.mask_start,
                       d.mask_end, d.B, c.in_channels, c.sample_h, Wx};
@@ -942,12 +942,54 @@ int adm_sample_loop_philox(adm_unet_t* h, float* x, int B, const adm_sched_coef*
 
 int adm_unet_loop_captures(adm_unet_t* h) { return h ? h->captures : 0; }
 
+// The inversion loop: all argument checks are here. The fields it honours are x, B, coef_host, n_steps, use_graph, prediction and the three
+// window fields; every other one is a feature of the sampling step that the inversion step does not have, and is refused by its name.
+int adm_encode_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream) {
+  ADM_REQUIRE(h && a && a->x && a->coef_host && a->n_steps > 0 && a->B > 0, "encode_loop: bad argument");
+  ADM_REQUIRE(a->mode == SCHED_PLAIN, "encode_loop: mode must be 0 (the inversion step is not thresholded and not multistep)");
+  ADM_REQUIRE(a->prediction >= PRED_EPSILON && a->prediction <= PRED_V, "encode_loop: prediction must be 0 (epsilon), 1 (sample) or 2 (v_prediction)");
+  ADM_REQUIRE(a->k_hist_host == nullptr, "encode_loop: k_hist_host must be NULL (inversion is a DDIM procedure)");
+  ADM_REQUIRE(a->unipc_host == nullptr, "encode_loop: unipc_host must be NULL (inversion is a DDIM procedure)");
+  ADM_REQUIRE(a->step_noise == nullptr, "encode_loop: step_noise must be NULL (inversion is deterministic)");
+  ADM_REQUIRE(a->noise_source == 0, "encode_loop: noise_source must be 0 (inversion is deterministic)");
+  ADM_REQUIRE(a->seed == 0, "encode_loop: seed must be 0 (inversion is deterministic)");
+  ADM_REQUIRE(a->row_offset == 0, "encode_loop: row_offset must be 0 (inversion is deterministic)");
+  ADM_REQUIRE(a->mask == nullptr, "encode_loop: mask must be NULL");
+  ADM_REQUIRE(a->mask_start == 0, "encode_loop: mask_start must be 0");
+  ADM_REQUIRE(a->mask_end == 0, "encode_loop: mask_end must be 0");
+  ADM_REQUIRE(a->u8_out == nullptr, "encode_loop: u8_out must be NULL (the result is noise, not an image)");
+  ADM_REQUIRE(a->lo == 0, "encode_loop: lo must be 0 (the inversion step is not thresholded)");
+  ADM_REQUIRE(a->hi == 0, "encode_loop: hi must be 0 (the inversion step is not thresholded)");
+  ADM_REQUIRE(a->w == 0.f, "encode_loop: w must be 0 (the inversion step is not thresholded)");
+  ADM_REQUIRE(a->max_value == 0.f, "encode_loop: max_value must be 0 (the inversion step is not thresholded)");
+  ADM_REQUIRE(a->encoding_uncond == nullptr, "encode_loop: encoding_uncond must be NULL (guided inversion is not offered)");
+  ADM_REQUIRE(a->guidance_scale == 0.f, "encode_loop: guidance_scale must be 0 (guided inversion is not offered)");
+  ADM_REQUIRE(a->guidance_rescale == 0.f, "encode_loop: guidance_rescale must be 0 (guided inversion is not offered)");
+  ADM_REQUIRE(a->keep == nullptr, "encode_loop: keep must be NULL (inversion has no known region)");
+  ADM_REQUIRE(a->known == nullptr, "encode_loop: known must be NULL (inversion has no known region)");
+  ADM_REQUIRE(a->known_noise == nullptr, "encode_loop: known_noise must be NULL (inversion has no known region)");
+  ADM_REQUIRE(a->known_coef_host == nullptr, "encode_loop: known_coef_host must be NULL (inversion has no known region)");
+  ADM_REQUIRE(a->known_batched == 0, "encode_loop: known_batched must be 0 (inversion has no known region)");
+  ADM_REQUIRE(a->keep_batched == 0, "encode_loop: keep_batched must be 0 (inversion has no known region)");
+  adm_sample_loop_args e = *a;
+  if (a->window_total_w != 0) {   // windowed (include/adm.h "Windowed sampling"); 0: off, and window_stride / window_wrap are ignored
+    int nW = 0;
+    ADM_TRY(window_count("encode_loop", "window_", a->window_total_w, h->cfg.sample_w, a->window_stride, a->window_wrap, &nW));
+    ADM_REQUIRE((long)a->B * nW <= 2147483647L, "encode_loop: B times the number of windows (window_total_w, window_stride) must fit in an int");
+  } else {
+    e.window_stride = e.window_wrap = 0;
+  }
+  ADM_REQUIRE(((long)a->B * h->cfg.in_channels * h->cfg.sample_h * (a->window_total_w != 0 ? a->window_total_w : h->cfg.sample_w)) % 4 == 0,
+              "encode_loop: B*C*H*W must be a multiple of 4");
+  e.mode = LOOP_ENCODE;
+  return run_loop_fp32(h, e, stream);
+}
+
+// FROZEN: a struct fill and one call
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream) {
-  ADM_REQUIRE(h && x && coef_host && n_steps > 0, "encode_loop: bad argument");
-  adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, nullptr, nullptr, 0, 0, nullptr, use_graph);
-  a.mode = LOOP_ENCODE;
-  return run_loop_fp32(h, a, stream);
+  const adm_sample_loop_args a = loop_args(x, B, coef_host, n_steps, nullptr, nullptr, 0, 0, nullptr, use_graph);
+  return adm_encode_loop_ex(h, &a, stream);
 }
 
 }  // extern "C"

@@ -794,8 +794,31 @@ typedef struct adm_sample_loop_args {
   int known_batched, keep_batched;
 } adm_sample_loop_args;
 int adm_sample_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
-/* DDIM inversion loop (row P6, pipeline_audio_diffusion.py:228-240): per step
- *   x = (x - c_dir*eps) * c_inv * c_fwd + c_eps*eps  with coef {sqrt_beta=c_dir, sqrt_alpha=c_inv, k_x0=c_fwd, k_eps=c_eps}. */
+/* DDIM inversion (row P6, pipeline_audio_diffusion.py:228-240; the other prediction types, the conditional model and the windowed loop:
+ * adm_version() >= 123). x is the sample at level s, o the model output, t the target level and c the level of the timestep the model was
+ * given; sa = sqrt(alphas_cumprod), sb = sqrt(1 - alphas_cumprod):
+ *   e  = o (epsilon)     e = (x - sa_c*o) / sb_c (sample)     e = sa_c*o + sb_c*x (v_prediction)       -- the table of adm_sched_step_pred
+ *   x' = ((x - sb_s*e) * (1/sa_s)) * sa_t + sb_t*e
+ * What the eight adm_sched_coef fields mean in an inversion row:
+ *   sqrt_beta = sb_s    sqrt_alpha = 1/sa_s (NOT sa_s)    k_x0 = sa_t    k_eps = sb_t    timestep = the timestep the model is given
+ *   k_x = sa_c          k_noise = sb_c                    clip: not read (the schedulers write -1)
+ * An epsilon row reads neither k_x nor k_noise (the schedulers leave both 0 there, as before version 123). The reference's rule gives
+ * the model the TARGET timestep (c = t); the textbook rule gives it the sample's own (c = s, DDIMScheduler.encode_rows(level="matched")).
+ * On a zero-SNR row (sa_c = 0, sb_c = 1) the two new forms give e = x and stay finite; a sample row with sb_c = 0 is out of contract, as
+ * in adm_sched_step_pred. A first row with sa_s = 1, sb_s = 0 (final_alpha_cumprod = 1) leaves x0 = x exactly.
+ * adm_encode_step: ONE step on n elements (n % 4 == 0), in place; row = step_dev ? *step_dev : step; prediction 0, 1, 2 as above. */
+int adm_encode_step(float* x, const float* model_out, const adm_sched_coef* coef_table, const int* step_dev, int step, int prediction,
+                    long n, void* stream);
+/* The inversion loop (adm_version() >= 123): per step the forward at coef_host[i].timestep, then adm_encode_step. It takes the struct of
+ * adm_sample_loop_ex and honours x, B, coef_host, n_steps, use_graph, prediction and window_total_w / window_stride / window_wrap (the
+ * windowed step is the sampling loop's: gather, ONE forward at batch B*nW, blend, the inversion step at the wide shape). Every other
+ * field must be NULL / 0 and is refused by its name otherwise (mode included: adm_sample_loop_ex in turn has no inversion mode). A
+ * conditional handle reads its encoding (adm_unet_set_encoding; B*nW rows, sample-major, when windowed); there is no guided inversion.
+ * The captured step is keyed as the sampling loop's: new table values at the same n_steps replay, another prediction or window
+ * placement captures again, and one handle may alternate inversion and sampling loops.
+ * FROZEN: adm_encode_loop keeps its signature and results (epsilon, unconditional or not, the model's width); it fills the struct and
+ * calls adm_encode_loop_ex. */
+int adm_encode_loop_ex(adm_unet_t* h, const adm_sample_loop_args* a, void* stream);
 int adm_encode_loop(adm_unet_t* h, float* x, int B, const adm_sched_coef* coef_host, int n_steps, int use_graph,
                     void* stream);
 /* Test aid (adm_version() >= 122): how many times this handle has captured a step since it was created (0 for NULL). The emulation build
